@@ -8,9 +8,19 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W`;
 for N>1 the driver launches via torch.distributed.run with one rank per
 GPU over RCCL.  Rank 0 prints ONE JSON line.  Weak scaling: per-GPU
 batch fixed at 128 as N grows.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time K steps, print the result line.  `--dump-outputs DIR` additionally
+writes what the last timed step computed as DIR/<name>.npy so that two
+builds can be compared output for output (inputs, initial weights and
+the sampled indices are all seeded, identical from run to run).
+`--full` is the switch for secondary measurements; this harness has
+none of its own (kernel-level benchmarks live under benchmarks/), so it
+currently runs the same measurement as a plain run.
 """
 
 import argparse
+import contextlib
 import json
 import os
 import time
@@ -43,7 +53,46 @@ def parse():
     # wherever activations fit in the 288 GB)
     p.add_argument("--grad_ckpt_blocks", type=int, default=-2)
     p.add_argument("--fuse_residual", action="store_true")
+    # where the synthetic initial weights are drawn.  "device" (default)
+    # builds the model under the device context, so the ~10^10 uniform
+    # draws of ViT-10B come from the GPU generator in well under a
+    # second; "host" is the trainer's path (serial CPU generator, ~30 s
+    # at ViT-10B, then a host-to-device copy per block).  Same
+    # distributions and same seed either way, different random streams.
+    p.add_argument("--init", type=str, default="device",
+                   choices=["device", "host"])
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write the last step's "
+                        "outputs as DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run secondary measurements (none in this "
+                        "harness today: same as a plain run)")
     return p.parse_args()
+
+
+def dump_outputs(out_dir, last, model):
+    """Write what the last timed step handed back (loss, logits, full
+    gradient norm) plus a fixed seeded sample of the fp32 master weights
+    it updated, as float32 .npy files (~1 MB in all at ViT-10B)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "loss": last["loss"].detach().reshape(1),
+        "logits": last["logits"],
+    }
+    if last.get("grad_norm") is not None:
+        arrays["grad_norm"] = last["grad_norm"].detach().reshape(1)
+    gen = torch.Generator(device="cpu").manual_seed(2024)
+    picks = []
+    for prm in model.parameters():
+        flat = prm.detach().reshape(-1)
+        idx = torch.randint(0, flat.numel(), (4096,), generator=gen)
+        picks.append(flat[idx.to(flat.device)].float().cpu())
+    arrays["params_sample"] = torch.cat(picks)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.float().cpu().numpy().astype(np.float32))
 
 
 def auto_ckpt_blocks(args, world, img, patch, embed, blocks, mlp_ratio,
@@ -135,7 +184,10 @@ def main():
 
     torch.manual_seed(1234)
     t_build = time.time()
-    model = build_fsdp_vit_model(cfg, device, compute_dtype=compute_dtype)
+    on_device_init = (args.init == "device" and device.type == "cuda"
+                      and not args.shard_on_cpu)
+    with torch.device(device) if on_device_init else contextlib.nullcontext():
+        model = build_fsdp_vit_model(cfg, device, compute_dtype=compute_dtype)
     loss_fn = CrossEntropyLoss()
     opt = FusedAdamW(model.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
     sched = get_warmup_cosine_scheduler(opt, cfg.warmup_steps, 10**9)
@@ -152,18 +204,24 @@ def main():
         y = torch.randint(0, classes, (b,), generator=gen).to(device)
         batches.append((x, y))
 
+    last = {}  # what the most recent step computed (for --dump-outputs)
+
     def one_step(i):
         x, y = batches[i % 2]
         # dispatch-level GEMM rerouting (tuned hipBLASLt indices /
         # native wgrad) covers forward, recompute and backward
         with gemm_dispatch_context():
-            loss = loss_fn(model(x), y)
+            logits = model(x)
+            loss = loss_fn(logits, y)
             loss.backward()
+        grad_norm = None
         if cfg.clip_grad_norm > 0:
-            model.clip_grad_norm_(cfg.clip_grad_norm, defer_scale=True)
+            grad_norm = model.clip_grad_norm_(cfg.clip_grad_norm,
+                                              defer_scale=True)
         opt.step()
         sched.step()
         opt.zero_grad(set_to_none=True)
+        last.update(loss=loss, logits=logits.detach(), grad_norm=grad_norm)
         return loss
 
     def barrier_sync():
@@ -188,6 +246,9 @@ def main():
         t = t.to(device) if device.type == "cuda" else t
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0 and last:
+        dump_outputs(args.dump_outputs, last, model)
 
     images_per_sec = args.steps * b * world / elapsed
     ms_per_step = elapsed * 1000.0 / args.steps
@@ -226,6 +287,7 @@ def main():
                 "grad_ckpt": cfg.grad_ckpt,
                 "grad_ckpt_blocks": args.grad_ckpt_blocks,
                 "fuse_residual": args.fuse_residual,
+                "init": "device" if on_device_init else "host",
                 "final_loss": float(loss.item()) if loss is not None else None,
             },
         }

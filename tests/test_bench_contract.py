@@ -146,3 +146,47 @@ def test_bench_torchrun_ws4():
     assert out["n_gpus"] == 4
     assert out["config"]["global_batch"] == 8
     assert out["config"]["parallelism"] == "fsdp4"
+
+
+def _run_bench(*extra):
+    res = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--model", "vit-tiny",
+         "--per_gpu_batch", "2", "--steps", "2", "--warmup", "1", *extra],
+        capture_output=True, text=True, cwd=REPO, timeout=600,
+    )
+    assert res.returncode == 0, res.stderr[-2000:]
+    json_lines = [ln for ln in res.stdout.splitlines()
+                  if ln.startswith("{") and ln.endswith("}")]
+    assert len(json_lines) == 1, res.stdout[-2000:]
+    return json.loads(json_lines[0])
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs DIR writes the last timed step's outputs as
+    float32 .npy files; inputs and initial weights are seeded, so two
+    runs (one plain, one with --full) agree — exactly on CPU, where the
+    eager ops are deterministic.  --full keeps the result line's shape."""
+    import numpy as np
+
+    a, b = tmp_path / "a", tmp_path / "b"
+    out_a = _run_bench("--dump-outputs", str(a))
+    out_b = _run_bench("--dump-outputs", str(b), "--full")
+    assert out_a["steps"] == out_b["steps"] == 2
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert out_a[key] == out_b[key], key
+    assert out_b["ms_per_step"] > 0
+
+    names = sorted(p.name for p in a.iterdir())
+    assert names == ["grad_norm.npy", "logits.npy", "loss.npy",
+                     "params_sample.npy"]
+    total = 0
+    for name in names:
+        x, y = np.load(a / name), np.load(b / name)
+        assert x.dtype == np.float32 and np.isfinite(x).all(), name
+        assert x.shape == y.shape and np.array_equal(x, y), name
+        total += x.nbytes
+    assert total <= 64 * 2**20
+    assert np.load(a / "logits.npy").shape == (2, 1000)
+    # the dumped loss IS the last timed step's loss
+    loss = float(np.load(a / "loss.npy")[0])
+    assert abs(loss - out_a["config"]["final_loss"]) < 1e-6
