@@ -22,11 +22,7 @@ sanitize:
 	bash csrc/tools/sanitize_build.sh
 
 resources:
-	@for f in csrc/*.hip; do \
-	  case $$f in *_hip.hip) continue;; esac; \
-	  echo "== $$f"; bash csrc/tools/check_resources.sh $$f 2>&1 | \
-	    grep -E "kernel-resource-usage|SGPRs|VGPRs|LDS|Occupancy" | head -20; \
-	done
+	@bash csrc/tools/check_resources.sh $$(ls csrc/*.hip | grep -v '_hip\.hip$$')
 
 clean:
 	rm -rf build vit_10b_fsdp_example_amd/_C*.so csrc/*_hip.hip

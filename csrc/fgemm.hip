@@ -11,10 +11,7 @@
 // same 256x256x64 tile, 512 threads as 2m x 4n waves of 128x64, double
 // buffered LDS, next-step global loads issued under the MFMA phases).
 //
-// MFMA fragment layout (pinned on-device by mfma_probe,
-// tests/test_gpu_kernels.py): lane l of the wave contributes row (l&15)
-// of A and column (l&15) of B, k-slice (l>>4)*8 .. +8; the f32x4 result
-// holds rows (l>>4)*4 .. +4 of column (l&15).
+// MFMA fragment layouts (16x16x32 and 32x32x16): mfma_tiles.h.
 
 #ifndef VITFSDP_KERNELS_ONLY
 #include <ATen/cuda/CUDAContext.h>
@@ -23,12 +20,9 @@
 #include <cstdlib>
 #endif
 
-#include "common.h"
+#include "mfma_tiles.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int kBM = 256;
 constexpr int kBN = 256;
@@ -129,8 +123,7 @@ __global__ __launch_bounds__(kThreads, BK == 64 ? 1 : 2) void fgemm_abt_kernel(
       bx = (xcd % sx) * lw + band * gm + (r % gm);
       by = (xcd / sx) * lh + r / gm;
     } else if ((nwg & 7) == 0) {
-      const int cpx = nwg >> 3;
-      const int swz = (bid & 7) * cpx + (bid >> 3);
+      const int swz = xcd_swizzle_m_major(bid, nwg);
       bx = swz % gx;
       by = swz / gx;
     }
@@ -309,8 +302,6 @@ __global__ __launch_bounds__(kThreads, BK == 64 ? 1 : 2) void fgemm_abt_kernel(
   }
 }
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 // Wide-MFMA variant: mfma_f32_32x32x16_bf16 halves the MFMA instruction
 // count per FLOP (the 16x16 kernel measured VALUBusy 27% competing with
 // MFMA issue at MfmaUtil 53%).  BK=64 + DirectToLds staging + the same
@@ -353,8 +344,7 @@ __global__ __launch_bounds__(kThreads, 1) void fgemm_abt_mi32_kernel(
       bx = (xcd % sx) * lw + band * gm + (r % gm);
       by = (xcd / sx) * lh + r / gm;
     } else if ((nwg & 7) == 0) {
-      const int cpx = nwg >> 3;
-      const int swzb = (bid & 7) * cpx + (bid >> 3);
+      const int swzb = xcd_swizzle_m_major(bid, nwg);
       bx = swzb % gx;
       by = swzb / gx;
     }

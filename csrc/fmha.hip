@@ -31,11 +31,8 @@
 // own reduction kernel.  No batched GEMM library calls (the hipBLASLt
 // composition survives as a debug path, VITFSDP_FMHA_BWD=compose).
 //
-// MFMA fragment layout (verified on-device by mfma_probe,
-// tests/test_gpu_kernels.py::test_mfma_probe_layout):
-//   A[i][k]: lane l holds a[j] = A[l&15][(l>>4)*8 + j]
-//   B[k][j]: lane l holds b[j] = B[(l>>4)*8 + j][l&15]
-//   C[i][j]: lane l holds c[r] = C[(l>>4)*4 + r][l&15]
+// MFMA fragment layouts, transpose-read semantics and the shared
+// ring / pack / reshuffle / fragment-load helpers: mfma_tiles.h.
 
 // Compile with -DVITFSDP_KERNELS_ONLY to build just the device kernels
 // (no torch headers) — used by csrc/tools/check_resources.sh for
@@ -46,15 +43,12 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #endif
 
-#include "common.h"
+#include "mfma_tiles.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 constexpr int kBlockThreads = 256;
 constexpr int kKTile = 32;  // k rows per inner iteration
@@ -138,9 +132,6 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_fwd_kernel(
   constexpr int DP = S::DP, NKC = S::NKC, NC = S::NC;
   constexpr int kQSub = S::QSub;
   constexpr int kQTile = S::QTile;
-  // loads per thread per K/V tile (16-byte vectors)
-  constexpr int kKVecs = (kKTile * (DP / 8) + kBlockThreads - 1) / kBlockThreads;
-  constexpr int kVVecs = (kKTile * (D / 8) + kBlockThreads - 1) / kBlockThreads;
   HIP_DYNAMIC_SHARED(char, smem_raw)
   typename S::Shared& sm = *reinterpret_cast<typename S::Shared*>(smem_raw);
 
@@ -157,21 +148,12 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_fwd_kernel(
   const long qkv_off = (long)b_idx * st.qb + (long)h_idx * st.qh;
   const long o_off = (long)b_idx * st.ob + (long)h_idx * st.oh;
 
-  // ---- hoisted staging coordinates (reused every K/V tile) ----
-  int k_kr[kKVecs], k_dc[kKVecs];
-#pragma unroll
-  for (int i = 0; i < kKVecs; ++i) {
-    const int idx = (int)threadIdx.x + i * kBlockThreads;
-    k_kr[i] = idx / (DP / 8);
-    k_dc[i] = (idx % (DP / 8)) * 8;
-  }
-  int v_kr[kVVecs], v_dc[kVVecs];
-#pragma unroll
-  for (int i = 0; i < kVVecs; ++i) {
-    const int idx = (int)threadIdx.x + i * kBlockThreads;
-    v_kr[i] = idx / (D / 8);
-    v_dc[i] = (idx % (D / 8)) * 8;
-  }
+  // ---- hoisted staging coordinates (reused every K/V tile): the K
+  // tile is zero-padded to DP columns for QK^T, the V tile is D wide ----
+  using KStage = TileStage<kKTile, DP, D, kBlockThreads>;
+  using VStage = TileStage<kKTile, D, D, kBlockThreads>;
+  const KStage k_stg;
+  const VStage v_stg;
 
   // ---- load Q fragments to registers: sub-tile qs, chunk kc, elem j ->
   // Q[q_row0 + 16*qs + col][seg*8 + j + 32*kc] (zero-padded beyond D/T) --
@@ -179,22 +161,8 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_fwd_kernel(
 #pragma unroll
   for (int qs = 0; qs < kQSub; ++qs) {
     const int q_row = q_row0 + 16 * qs + col;
-    const bool valid = q_row < T;
-    const long base = qkv_off + (long)q_row * st.qt;
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      const int d0 = kc * 32 + seg * 8;
-      if (valid && d0 + 8 <= D) {
-        // contiguous 8 elements: one 16-B load instead of 8 scalars
-        q_frag[qs][kc] = *reinterpret_cast<const bf16x8*>(&q[base + d0]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          q_frag[qs][kc][j] =
-              (valid && d0 + j < D) ? q[base + d0 + j] : (short)0;
-        }
-      }
-    }
+    load_row_frags<NKC, D>(q + qkv_off + (long)q_row * st.qt, q_row < T, seg,
+                           q_frag[qs]);
   }
 
   // ---- online softmax state: ONE q row per lane (q = col) ----
@@ -213,50 +181,15 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_fwd_kernel(
   // latency hides under the MFMA phases; the LDS writes land after) ----
   // K and V staging share one register block: their live ranges are
   // disjoint (K: issue -> write before PV; V: issue -> write after PV)
-  constexpr int kStageVecs = kKVecs > kVVecs ? kKVecs : kVVecs;
-  bf16x8 stage[kStageVecs];
+  bf16x8 stage[KStage::N > VStage::N ? KStage::N : VStage::N];
   auto issue_k_loads = [&](int k_base) {
-#pragma unroll
-    for (int i = 0; i < kKVecs; ++i) {
-      bf16x8 val = {0, 0, 0, 0, 0, 0, 0, 0};
-      const int k_row = k_base + k_kr[i];
-      if (k_kr[i] < kKTile && k_row < T && k_dc[i] < D) {
-        val = *reinterpret_cast<const bf16x8*>(
-            &k[qkv_off + (long)k_row * st.qt + k_dc[i]]);
-      }
-      stage[i] = val;
-    }
+    k_stg.load(k + qkv_off, st.qt, k_base, T, stage);
   };
-  auto write_k_tile = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < kKVecs; ++i) {
-      if (k_kr[i] < kKTile) {
-        *reinterpret_cast<bf16x8*>(&sm.k_tile[buf][k_kr[i]][k_dc[i]]) =
-            stage[i];
-      }
-    }
-  };
+  auto write_k_tile = [&](int buf) { k_stg.store(sm.k_tile[buf], stage); };
   auto issue_v_loads = [&](int k_base) {
-#pragma unroll
-    for (int i = 0; i < kVVecs; ++i) {
-      bf16x8 val = {0, 0, 0, 0, 0, 0, 0, 0};
-      const int k_row = k_base + v_kr[i];
-      if (v_kr[i] < kKTile && k_row < T) {
-        val = *reinterpret_cast<const bf16x8*>(
-            &v[qkv_off + (long)k_row * st.qt + v_dc[i]]);
-      }
-      stage[i] = val;
-    }
+    v_stg.load(v + qkv_off, st.qt, k_base, T, stage);
   };
-  auto write_v_tile = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < kVVecs; ++i) {
-      if (v_kr[i] < kKTile) {
-        *reinterpret_cast<bf16x8*>(&sm.v_tile[buf][v_kr[i]][v_dc[i]]) =
-            stage[i];
-      }
-    }
-  };
+  auto write_v_tile = [&](int buf) { v_stg.store(sm.v_tile[buf], stage); };
 
   const int n_ktiles = (T + kKTile - 1) / kKTile;
   // prologue: stage tile 0 into buffer 0
@@ -356,37 +289,10 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_fwd_kernel(
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-          pk[kk][rr] = (unsigned)f32_to_bf16(p[kk][2 * rr]) |
-                       ((unsigned)f32_to_bf16(p[kk][2 * rr + 1]) << 16);
-        }
+        for (int rr = 0; rr < 2; ++rr)
+          pk[kk][rr] = pack_bf16x2(p[kk][2 * rr], p[kk][2 * rr + 1]);
       }
-      // redistribute to the MFMA A layout: target elem pair j2 wants
-      // k = seg*8 + 2*j2 of its own q=col, which lives in lane
-      // col + 16*((seg&1)*2 + (j2>>1)), slot (kk=seg>>1, rr=j2&1).
-      // A source lane serves targets from BOTH kk halves, so shuffle
-      // both kk slots and let each target select by its own seg.
-      const int kk_s = seg >> 1;
-      unsigned pa_u[4];
-#pragma unroll
-      for (int j2 = 0; j2 < 4; ++j2) {
-        const int src = col + 16 * ((seg & 1) * 2 + (j2 >> 1));
-        const unsigned lo = (unsigned)__shfl((int)pk[0][j2 & 1], src);
-        const unsigned hi = (unsigned)__shfl((int)pk[1][j2 & 1], src);
-        pa_u[j2] = kk_s ? hi : lo;
-      }
-      bf16x8 pa;
-      {
-        union {
-          unsigned u[4];
-          bf16x8 v;
-        } cvt;
-        cvt.u[0] = pa_u[0];
-        cvt.u[1] = pa_u[1];
-        cvt.u[2] = pa_u[2];
-        cvt.u[3] = pa_u[3];
-        pa = cvt.v;
-      }
+      const bf16x8 pa = c_to_a_layout(pk, seg, col);
 
       // rescale O: its C-layout rows are q = seg*4 + r, whose alpha
       // lives in lane (seg*4 + r) of the column group
@@ -406,52 +312,13 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_fwd_kernel(
 
       // ---- O += P V : NC chunks of 16 output columns ----
       // B fragments come from the ROW-major V tile via
-      // ds_read_b64_tr_b16 (2 transpose reads per 16-column chunk,
-      // 2-deep ring with counted waits): the element-wise transposed
+      // transpose reads (mfma_tr_ring): the element-wise transposed
       // store and its bank-conflict swizzle are gone entirely.
       const unsigned v_lds_base =
           (unsigned)__builtin_amdgcn_groupstaticsize() +
           (unsigned)(offsetof(typename S::Shared, v_tile)) +
           (unsigned)cur * (unsigned)sizeof(sm.v_tile[0]);
-      auto v_tr = [&](int c, int h) -> u32x2 {
-        const unsigned addr =
-            v_lds_base +
-            2u * ((unsigned)((seg * 8 + 4 * h + (col >> 2)) * S::VRow +
-                             c * 16 + (col & 3) * 4));
-        u32x2 r;
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0"
-                     : "=v"(r)
-                     : "v"(addr));
-        return r;
-      };
-      u32x2 vf[2][2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) vf[0][h] = v_tr(0, h);
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int curc = c & 1;
-        if (c + 1 < NC) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h) vf[curc ^ 1][h] = v_tr(c + 1, h);
-          asm volatile("s_waitcnt lgkmcnt(%[cnt])"
-                       : "+v"(vf[curc][0]), "+v"(vf[curc][1])
-                       : [cnt] "i"(2)
-                       : "memory");
-        } else {
-          asm volatile("s_waitcnt lgkmcnt(%[cnt])"
-                       : "+v"(vf[curc][0]), "+v"(vf[curc][1])
-                       : [cnt] "i"(0)
-                       : "memory");
-        }
-        union {
-          u32x2 uu[2];
-          bf16x8 v;
-        } vc;
-        vc.uu[0] = vf[curc][0];
-        vc.uu[1] = vf[curc][1];
-        o_acc[qs][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            pa, vc.v, o_acc[qs][c], 0, 0, 0);
-      }
+      mfma_tr_ring<NC, S::VRow>(pa, v_lds_base, seg, col, o_acc[qs]);
     }
 
     if (has_next) write_v_tile(cur ^ 1);
@@ -520,24 +387,10 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_bwd_dq_kernel(
   for (int qs = 0; qs < kQSub; ++qs) {
     const int q_row = q_row0 + 16 * qs + col;
     const bool valid = q_row < T;
-    const long base = qkv_off + (long)q_row * st.qt;
-    const long dbase = o_off + (long)q_row * st.ot;
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      const int d0 = kc * 32 + seg * 8;
-      if (valid && d0 + 8 <= D) {
-        q_frag[qs][kc] = *reinterpret_cast<const bf16x8*>(&q[base + d0]);
-        do_frag[qs][kc] =
-            *reinterpret_cast<const bf16x8*>(&dout[dbase + d0]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const bool ok = valid && d0 + j < D;
-          q_frag[qs][kc][j] = ok ? q[base + d0 + j] : (short)0;
-          do_frag[qs][kc][j] = ok ? dout[dbase + d0 + j] : (short)0;
-        }
-      }
-    }
+    load_row_frags<NKC, D>(q + qkv_off + (long)q_row * st.qt, valid, seg,
+                           q_frag[qs]);
+    load_row_frags<NKC, D>(dout + o_off + (long)q_row * st.ot, valid, seg,
+                           do_frag[qs]);
     // per-lane row stats: this lane's q row is q = col (swapped layout)
     lse_q[qs] = valid ? lse[bh * T + q_row] : 0.f;
     delta_q[qs] = valid ? delta[bh * T + q_row] : 0.f;
@@ -549,39 +402,17 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_bwd_dq_kernel(
 #pragma unroll
     for (int c = 0; c < NC; ++c) dq_acc[qs][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // hoisted staging coordinates + register staging for the K/V tiles
-  constexpr int kLVecs = (kKTile * (DP / 8) + kBlockThreads - 1) / kBlockThreads;
-  int l_kr[kLVecs], l_dc[kLVecs];
-#pragma unroll
-  for (int i = 0; i < kLVecs; ++i) {
-    const int idx = (int)threadIdx.x + i * kBlockThreads;
-    l_kr[i] = idx / (DP / 8);
-    l_dc[i] = (idx % (DP / 8)) * 8;
-  }
-  bf16x8 kst[kLVecs], vst[kLVecs];
+  // register staging for the K/V tiles (one coordinate set serves both)
+  using Stage = TileStage<kKTile, DP, D, kBlockThreads>;
+  const Stage stg;
+  bf16x8 kst[Stage::N], vst[Stage::N];
   auto issue_kv_loads = [&](int k_base) {
-#pragma unroll
-    for (int i = 0; i < kLVecs; ++i) {
-      bf16x8 kv = {0, 0, 0, 0, 0, 0, 0, 0};
-      bf16x8 vv = {0, 0, 0, 0, 0, 0, 0, 0};
-      const int k_row = k_base + l_kr[i];
-      if (l_kr[i] < kKTile && k_row < T && l_dc[i] < D) {
-        kv = *reinterpret_cast<const bf16x8*>(
-            &k[qkv_off + (long)k_row * st.qt + l_dc[i]]);
-        vv = *reinterpret_cast<const bf16x8*>(
-            &v[qkv_off + (long)k_row * st.qt + l_dc[i]]);
-      }
-      kst[i] = kv;
-      vst[i] = vv;
-    }
+    stg.load(k + qkv_off, st.qt, k_base, T, kst);
+    stg.load(v + qkv_off, st.qt, k_base, T, vst);
   };
   auto write_kv_tiles = [&]() {
-#pragma unroll
-    for (int i = 0; i < kLVecs; ++i) {
-      if (l_kr[i] >= kKTile) continue;
-      *reinterpret_cast<bf16x8*>(&sm.k_tile[l_kr[i]][l_dc[i]]) = kst[i];
-      *reinterpret_cast<bf16x8*>(&sm.v_tile[l_kr[i]][l_dc[i]]) = vst[i];
-    }
+    stg.store(sm.k_tile, kst);
+    stg.store(sm.v_tile, vst);
   };
 
   const int n_ktiles = (T + kKTile - 1) / kKTile;
@@ -622,11 +453,10 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_bwd_dq_kernel(
       for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
-          unsigned packed = 0;
+          float ds[2] = {0.f, 0.f};
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const int r = 2 * rr + h;
-            float ds = 0.f;
             const int k_idx = k_base + 16 * kk + seg * 4 + r;
             if (k_idx < T) {
               const float pv =
@@ -639,81 +469,21 @@ __global__ __launch_bounds__(kBlockThreads, 3) void fmha_bwd_dq_kernel(
                          ? dp * drop_rscale
                          : 0.f;
               }
-              ds = scale * pv * (dp - delta_q[qs]);
+              ds[h] = scale * pv * (dp - delta_q[qs]);
             }
-            packed |= (unsigned)f32_to_bf16(ds) << (16 * h);
           }
-          pk[kk][rr] = packed;
+          pk[kk][rr] = pack_bf16x2(ds[0], ds[1]);
         }
       }
-      // redistribute dS to the MFMA A layout (same shuffle pattern as
-      // the forward's P)
-      const int kk_s = seg >> 1;
-      unsigned da_u[4];
-#pragma unroll
-      for (int j2 = 0; j2 < 4; ++j2) {
-        const int srcl = col + 16 * ((seg & 1) * 2 + (j2 >> 1));
-        const unsigned lo = (unsigned)__shfl((int)pk[0][j2 & 1], srcl);
-        const unsigned hi = (unsigned)__shfl((int)pk[1][j2 & 1], srcl);
-        da_u[j2] = kk_s ? hi : lo;
-      }
-      bf16x8 ds_frag;
-      {
-        union {
-          unsigned u[4];
-          bf16x8 v;
-        } cvt;
-        cvt.u[0] = da_u[0];
-        cvt.u[1] = da_u[1];
-        cvt.u[2] = da_u[2];
-        cvt.u[3] = da_u[3];
-        ds_frag = cvt.v;
-      }
+      const bf16x8 ds_frag = c_to_a_layout(pk, seg, col);
 
       // dQ += dS K: B fragments from the row-major K tile via hardware
-      // transpose reads (2-deep chunk ring, counted waits)
+      // transpose reads
       const unsigned k_lds_base =
           (unsigned)__builtin_amdgcn_groupstaticsize() +
           (unsigned)offsetof(typename S::SharedDQ, k_tile);
-      auto k_tr = [&](int c, int h) -> u32x2 {
-        const unsigned addr =
-            k_lds_base +
-            2u * ((unsigned)((seg * 8 + 4 * h + (col >> 2)) * S::KStride +
-                             c * 16 + (col & 3) * 4));
-        u32x2 r;
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0"
-                     : "=v"(r)
-                     : "v"(addr));
-        return r;
-      };
-      u32x2 kf[2][2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) kf[0][h] = k_tr(0, h);
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int curc = c & 1;
-        if (c + 1 < NC) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h) kf[curc ^ 1][h] = k_tr(c + 1, h);
-          asm volatile("s_waitcnt lgkmcnt(%[cnt])"
-                       : "+v"(kf[curc][0]), "+v"(kf[curc][1])
-                       : [cnt] "i"(2)
-                       : "memory");
-        } else {
-          asm volatile("s_waitcnt lgkmcnt(%[cnt])"
-                       : "+v"(kf[curc][0]), "+v"(kf[curc][1])
-                       : [cnt] "i"(0)
-                       : "memory");
-        }
-        union {
-          u32x2 uu[2];
-          bf16x8 v;
-        } kc2;
-        kc2.uu[0] = kf[curc][0];
-        kc2.uu[1] = kf[curc][1];
-        dq_acc[qs][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            ds_frag, kc2.v, dq_acc[qs][c], 0, 0, 0);
-      }
+      mfma_tr_ring<NC, S::KStride>(ds_frag, k_lds_base, seg, col,
+                                   dq_acc[qs]);
     }
 
     if (has_next) {
@@ -768,23 +538,9 @@ __global__ __launch_bounds__(kBlockThreads, 2) void fmha_bwd_dkv_kernel(
   bf16x8 k_frag[NKC], v_frag[NKC];
   {
     const int k_row = k_row0 + col;
-    const bool valid = k_row < T;
     const long base = qkv_off + (long)k_row * st.qt;
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      const int d0 = kc * 32 + seg * 8;
-      if (valid && d0 + 8 <= D) {
-        k_frag[kc] = *reinterpret_cast<const bf16x8*>(&k[base + d0]);
-        v_frag[kc] = *reinterpret_cast<const bf16x8*>(&v[base + d0]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const bool ok = valid && d0 + j < D;
-          k_frag[kc][j] = ok ? k[base + d0 + j] : (short)0;
-          v_frag[kc][j] = ok ? v[base + d0 + j] : (short)0;
-        }
-      }
-    }
+    load_row_frags<NKC, D>(k + base, k_row < T, seg, k_frag);
+    load_row_frags<NKC, D>(v + base, k_row < T, seg, v_frag);
   }
 
   f32x4 dk_acc[NC], dv_acc[NC];
@@ -794,39 +550,17 @@ __global__ __launch_bounds__(kBlockThreads, 2) void fmha_bwd_dkv_kernel(
     dv_acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  // hoisted staging coordinates (16B vectors of the q/dO tiles)
-  constexpr int kQVecs = (kQStream * (DP / 8) + kBlockThreads - 1) / kBlockThreads;
-  int s_qr[kQVecs], s_dc[kQVecs];
-#pragma unroll
-  for (int i = 0; i < kQVecs; ++i) {
-    const int idx = (int)threadIdx.x + i * kBlockThreads;
-    s_qr[i] = idx / (DP / 8);
-    s_dc[i] = (idx % (DP / 8)) * 8;
-  }
-  bf16x8 q_st[kQVecs], do_st[kQVecs];
+  // register staging for the q/dO tiles (one coordinate set serves both)
+  using Stage = TileStage<kQStream, DP, D, kBlockThreads>;
+  const Stage stg;
+  bf16x8 q_st[Stage::N], do_st[Stage::N];
   auto issue_qdo_loads = [&](int q_base) {
-#pragma unroll
-    for (int i = 0; i < kQVecs; ++i) {
-      bf16x8 qv = {0, 0, 0, 0, 0, 0, 0, 0};
-      bf16x8 dov = {0, 0, 0, 0, 0, 0, 0, 0};
-      const int q_row = q_base + s_qr[i];
-      if (s_qr[i] < kQStream && q_row < T && s_dc[i] < D) {
-        qv = *reinterpret_cast<const bf16x8*>(
-            &q[qkv_off + (long)q_row * st.qt + s_dc[i]]);
-        dov = *reinterpret_cast<const bf16x8*>(
-            &dout[o_off + (long)q_row * st.ot + s_dc[i]]);
-      }
-      q_st[i] = qv;
-      do_st[i] = dov;
-    }
+    stg.load(q + qkv_off, st.qt, q_base, T, q_st);
+    stg.load(dout + o_off, st.ot, q_base, T, do_st);
   };
   auto write_qdo_tiles = [&]() {
-#pragma unroll
-    for (int i = 0; i < kQVecs; ++i) {
-      if (s_qr[i] >= kQStream) continue;
-      *reinterpret_cast<bf16x8*>(&sm.q_tile[s_qr[i]][s_dc[i]]) = q_st[i];
-      *reinterpret_cast<bf16x8*>(&sm.do_tile[s_qr[i]][s_dc[i]]) = do_st[i];
-    }
+    stg.store(sm.q_tile, q_st);
+    stg.store(sm.do_tile, do_st);
   };
 
   const int n_qtiles = (T + kQStream - 1) / kQStream;
@@ -904,51 +638,8 @@ __global__ __launch_bounds__(kBlockThreads, 2) void fmha_bwd_dkv_kernel(
         base0 + (unsigned)offsetof(typename S::SharedDKV, q_tile);
     const unsigned do_lds_base =
         base0 + (unsigned)offsetof(typename S::SharedDKV, do_tile);
-    auto qdo_tr = [&](unsigned base, int c, int h) -> u32x2 {
-      const unsigned addr =
-          base + 2u * ((unsigned)((seg * 8 + 4 * h + (col >> 2)) * S::KStride +
-                                  c * 16 + (col & 3) * 4));
-      u32x2 r;
-      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0"
-                   : "=v"(r)
-                   : "v"(addr));
-      return r;
-    };
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      const unsigned tr_base = pass == 0 ? do_lds_base : q_lds_base;
-      const bf16x8 a_frag = pass == 0 ? pt_frag : dst_frag;
-      f32x4* accs = pass == 0 ? dv_acc : dk_acc;
-      u32x2 bfrag[2][2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) bfrag[0][h] = qdo_tr(tr_base, 0, h);
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int curc = c & 1;
-        if (c + 1 < NC) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-            bfrag[curc ^ 1][h] = qdo_tr(tr_base, c + 1, h);
-          asm volatile("s_waitcnt lgkmcnt(%[cnt])"
-                       : "+v"(bfrag[curc][0]), "+v"(bfrag[curc][1])
-                       : [cnt] "i"(2)
-                       : "memory");
-        } else {
-          asm volatile("s_waitcnt lgkmcnt(%[cnt])"
-                       : "+v"(bfrag[curc][0]), "+v"(bfrag[curc][1])
-                       : [cnt] "i"(0)
-                       : "memory");
-        }
-        union {
-          u32x2 uu[2];
-          bf16x8 v;
-        } bc2;
-        bc2.uu[0] = bfrag[curc][0];
-        bc2.uu[1] = bfrag[curc][1];
-        accs[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_frag, bc2.v,
-                                                          accs[c], 0, 0, 0);
-      }
-    }
+    mfma_tr_ring<NC, S::KStride>(pt_frag, do_lds_base, seg, col, dv_acc);
+    mfma_tr_ring<NC, S::KStride>(dst_frag, q_lds_base, seg, col, dk_acc);
     if (has_next) {
       __syncthreads();  // everyone is done reading tile qt
       write_qdo_tiles();
@@ -1026,82 +717,6 @@ __global__ __launch_bounds__(256) void fmha_dsoftmax_kernel(
   }
 }
 
-
-// ds_read_b64_tr_b16 semantics probe: fill LDS with the identity
-// pattern lds[i] = i (as raw u16), issue one transpose-read per lane at
-// a caller-chosen per-lane base expression, return each lane's 4
-// elements.  The GPU test decodes the (lane, elem) -> lds index map so
-// kernels can rely on it (no public ISA doc in this environment).
-__global__ __launch_bounds__(64) void tr16_probe_kernel(
-    unsigned short* __restrict__ out, int mode) {
-  HIP_DYNAMIC_SHARED(char, smem_raw)
-  unsigned short* lds = reinterpret_cast<unsigned short*>(smem_raw);
-  for (int i = threadIdx.x; i < 1024; i += 64) lds[i] = (unsigned short)i;
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  unsigned addr_elems;
-  switch (mode) {
-    case 0: addr_elems = 0; break;                                // uniform
-    case 1: addr_elems = (lane & 15) + (lane >> 4) * 64; break;   // guide map
-    case 2: addr_elems = (lane & 15) * 4; break;                  // 4/lane
-    default: addr_elems = lane * 4; break;
-  }
-  // byte address into LDS (dynamic region starts at 0: no static smem)
-  unsigned addr = addr_elems * 2 + (unsigned)__builtin_amdgcn_groupstaticsize();
-  u32x2 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0"
-               : "=v"(v)
-               : "v"(addr));
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  out[lane * 4 + 0] = (unsigned short)(v[0] & 0xffff);
-  out[lane * 4 + 1] = (unsigned short)(v[0] >> 16);
-  out[lane * 4 + 2] = (unsigned short)(v[1] & 0xffff);
-  out[lane * 4 + 3] = (unsigned short)(v[1] >> 16);
-}
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-// Layout probe for the WIDE MFMA (mfma_f32_32x32x16_bf16): one wave,
-// row-major fp32 A[32][16] / B[16][32], using the assumed gfx9-family
-// fragment maps (A: lane l row l&31, k (l>>5)*8+j; C: lane l col l&31,
-// row (l>>5)*4 + g*8 + r at acc[g*4+r]).  The GPU test compares against
-// torch.matmul to pin the layout before csrc/fgemm.hip relies on it.
-__global__ __launch_bounds__(64) void mfma32_probe_kernel(
-    const float* __restrict__ a, const float* __restrict__ b,
-    float* __restrict__ c) {
-  const int l = threadIdx.x;
-  union { unsigned short u[8]; bf16x8 v; } av, bv;
-  for (int j = 0; j < 8; ++j) {
-    av.u[j] = f32_to_bf16(a[(l & 31) * 16 + (l >> 5) * 8 + j]);
-    bv.u[j] = f32_to_bf16(b[((l >> 5) * 8 + j) * 32 + (l & 31)]);
-  }
-  f32x16 acc = {};
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av.v, bv.v, acc, 0, 0, 0);
-  for (int g = 0; g < 4; ++g)
-    for (int r = 0; r < 4; ++r)
-      c[((l >> 5) * 4 + g * 8 + r) * 32 + (l & 31)] = acc[g * 4 + r];
-}
-
-// Layout probe: one wave computes a single 16x16x32 MFMA from row-major
-// fp32 A[16][32], B[32][16] using the documented fragment maps; the GPU
-// test compares against torch.matmul to pin the layout assumptions.
-__global__ __launch_bounds__(64) void mfma_probe_kernel(
-    const float* __restrict__ a, const float* __restrict__ b,
-    float* __restrict__ c) {
-  const int lane = threadIdx.x & 63;
-  const int col = lane & 15, seg = lane >> 4;
-  bf16x8 af, bf;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    af[j] = (short)f32_to_bf16(a[col * 32 + seg * 8 + j]);
-    bf[j] = (short)f32_to_bf16(b[(seg * 8 + j) * 16 + col]);
-  }
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc, 0, 0, 0);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) c[(seg * 4 + r) * 16 + col] = acc[r];
-}
-
 #ifdef VITFSDP_KERNELS_ONLY
 // explicit instantiations so -Rpass-analysis reports the real configs
 template __global__ void fmha_fwd_kernel<160, false>(
@@ -1113,14 +728,19 @@ template __global__ void fmha_fwd_kernel<160, true>(
 template __global__ void fmha_fwd_kernel<64, false>(
     const short*, const short*, const short*, short*, float*, int, int,
     QkvStrides, float, unsigned, float, unsigned);
-template __global__ void fmha_bwd_dq_kernel<160, false>(
-    const short*, const short*, const short*, const short*, const float*,
-    const float*, short*, int, int, QkvStrides, float, unsigned, float,
-    unsigned);
-template __global__ void fmha_bwd_dkv_kernel<160, false>(
-    const short*, const short*, const short*, const short*, const float*,
-    const float*, short*, short*, int, int, QkvStrides, float, unsigned,
-    float, unsigned);
+#define VITFSDP_INSTANTIATE_BWD(D_, DROP_)                                  \
+  template __global__ void fmha_bwd_dq_kernel<D_, DROP_>(                    \
+      const short*, const short*, const short*, const short*, const float*,  \
+      const float*, short*, int, int, QkvStrides, float, unsigned, float,    \
+      unsigned);                                                             \
+  template __global__ void fmha_bwd_dkv_kernel<D_, DROP_>(                   \
+      const short*, const short*, const short*, const short*, const float*,  \
+      const float*, short*, short*, int, int, QkvStrides, float, unsigned,   \
+      float, unsigned);
+VITFSDP_INSTANTIATE_BWD(160, false)
+VITFSDP_INSTANTIATE_BWD(160, true)  // the dropout backward training uses
+VITFSDP_INSTANTIATE_BWD(64, false)  // QSub = 2
+#undef VITFSDP_INSTANTIATE_BWD
 #else
 struct FmhaArgs {
   const short *q, *k, *v;
@@ -1138,23 +758,29 @@ inline unsigned drop_threshold(float p) {
   return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
 }
 
+// one launch per kernel: f(std::bool_constant<DROP>, thresh, rscale, seed)
+template <typename F>
+void with_dropout(const FmhaArgs& a, F&& f) {
+  if (a.p_drop > 0.f) {
+    f(std::true_type{}, drop_threshold(a.p_drop), 1.f / (1.f - a.p_drop),
+      a.seed);
+  } else {
+    f(std::false_type{}, 0u, 1.f, 0u);
+  }
+}
+
 template <int D>
 void launch_fmha_fwd(const FmhaArgs& a, torch::Tensor& lse) {
   dim3 grid((unsigned)((long)a.B * a.H),
             (a.T + FmhaShapes<D>::QTile - 1) / FmhaShapes<D>::QTile);
   auto stream = at::cuda::getCurrentCUDAStream();
-  if (a.p_drop > 0.f) {
-    hipLaunchKernelGGL((fmha_fwd_kernel<D, true>), grid, dim3(kBlockThreads),
+  with_dropout(a, [&](auto drop, unsigned thr, float rs, unsigned seed) {
+    hipLaunchKernelGGL((fmha_fwd_kernel<D, decltype(drop)::value>), grid,
+                       dim3(kBlockThreads),
                        sizeof(typename FmhaShapes<D>::Shared), stream, a.q,
                        a.k, a.v, a.o, lse.data_ptr<float>(), a.T, a.H, a.st,
-                       a.scale, drop_threshold(a.p_drop),
-                       1.f / (1.f - a.p_drop), a.seed);
-  } else {
-    hipLaunchKernelGGL((fmha_fwd_kernel<D, false>), grid, dim3(kBlockThreads),
-                       sizeof(typename FmhaShapes<D>::Shared), stream, a.q,
-                       a.k, a.v, a.o, lse.data_ptr<float>(), a.T, a.H, a.st,
-                       a.scale, 0u, 1.f, 0u);
-  }
+                       a.scale, thr, rs, seed);
+  });
   HIP_CHECK_LAST();
 }
 
@@ -1165,38 +791,23 @@ void launch_fmha_bwd(const FmhaArgs& a, const torch::Tensor& lse,
   using S = FmhaShapes<D>;
   auto stream = at::cuda::getCurrentCUDAStream();
   const unsigned BH = (unsigned)((long)a.B * a.H);
-  const unsigned thr = drop_threshold(a.p_drop);
-  const float rs = a.p_drop > 0.f ? 1.f / (1.f - a.p_drop) : 1.f;
   dim3 grid_dq(BH, (a.T + S::QTile - 1) / S::QTile);
-  if (a.p_drop > 0.f) {
-    hipLaunchKernelGGL((fmha_bwd_dq_kernel<D, true>), grid_dq,
-                       dim3(kBlockThreads), sizeof(typename S::SharedDQ),
-                       stream, a.q, a.k, a.v, a.o /*dO*/,
-                       lse.data_ptr<float>(), delta.data_ptr<float>(), dq,
-                       a.T, a.H, a.st, a.scale, thr, rs, a.seed);
-  } else {
-    hipLaunchKernelGGL((fmha_bwd_dq_kernel<D, false>), grid_dq,
-                       dim3(kBlockThreads), sizeof(typename S::SharedDQ),
-                       stream, a.q, a.k, a.v, a.o /*dO*/,
-                       lse.data_ptr<float>(), delta.data_ptr<float>(), dq,
-                       a.T, a.H, a.st, a.scale, 0u, 1.f, 0u);
-  }
-  HIP_CHECK_LAST();
   dim3 grid_dkv(BH, (a.T + 63) / 64);
-  if (a.p_drop > 0.f) {
-    hipLaunchKernelGGL((fmha_bwd_dkv_kernel<D, true>), grid_dkv,
+  with_dropout(a, [&](auto drop, unsigned thr, float rs, unsigned seed) {
+    constexpr bool kDrop = decltype(drop)::value;
+    hipLaunchKernelGGL((fmha_bwd_dq_kernel<D, kDrop>), grid_dq,
+                       dim3(kBlockThreads), sizeof(typename S::SharedDQ),
+                       stream, a.q, a.k, a.v, a.o /*dO*/,
+                       lse.data_ptr<float>(), delta.data_ptr<float>(), dq,
+                       a.T, a.H, a.st, a.scale, thr, rs, seed);
+    HIP_CHECK_LAST();
+    hipLaunchKernelGGL((fmha_bwd_dkv_kernel<D, kDrop>), grid_dkv,
                        dim3(kBlockThreads), sizeof(typename S::SharedDKV),
                        stream, a.q, a.k, a.v, a.o /*dO*/,
                        lse.data_ptr<float>(), delta.data_ptr<float>(), dk, dv,
-                       a.T, a.H, a.st, a.scale, thr, rs, a.seed);
-  } else {
-    hipLaunchKernelGGL((fmha_bwd_dkv_kernel<D, false>), grid_dkv,
-                       dim3(kBlockThreads), sizeof(typename S::SharedDKV),
-                       stream, a.q, a.k, a.v, a.o /*dO*/,
-                       lse.data_ptr<float>(), delta.data_ptr<float>(), dk, dv,
-                       a.T, a.H, a.st, a.scale, 0u, 1.f, 0u);
-  }
-  HIP_CHECK_LAST();
+                       a.T, a.H, a.st, a.scale, thr, rs, seed);
+    HIP_CHECK_LAST();
+  });
 }
 
 #define VITFSDP_FMHA_DISPATCH(D_, expr)                               \
@@ -1231,6 +842,18 @@ QkvStrides contiguous_strides(int H, int T, int D) {
   st.ob = st.qb;
   st.oh = st.qh;
   st.ot = st.qt;
+  return st;
+}
+
+// qkv: [B, T, 3, H, D] contiguous; o / dO: [B, T, H, D]
+QkvStrides fused_qkv_strides(int T, int H, int D) {
+  QkvStrides st;
+  st.qt = 3L * H * D;
+  st.qb = (long)T * st.qt;
+  st.qh = D;
+  st.ot = (long)H * D;
+  st.ob = (long)T * st.ot;
+  st.oh = D;
   return st;
 }
 
@@ -1333,13 +956,7 @@ std::vector<torch::Tensor> fmha_fwd_qkv(torch::Tensor qkv, long num_heads,
             D = qkv.size(4);
   TORCH_CHECK(D % 16 == 0 && D <= kMaxD,
               "fmha: head_dim must be a multiple of 16 and <= ", kMaxD);
-  QkvStrides st;
-  st.qt = 3L * H * D;
-  st.qb = (long)T * st.qt;
-  st.qh = D;
-  st.ot = (long)H * D;
-  st.ob = (long)T * st.ot;
-  st.oh = D;
+  const QkvStrides st = fused_qkv_strides(T, H, D);
 
   auto o = torch::empty({B, T, (long)H * D}, qkv.options());
   auto lse = torch::empty({B, H, T}, qkv.options().dtype(torch::kFloat32));
@@ -1358,13 +975,7 @@ torch::Tensor fmha_bwd_qkv(torch::Tensor dout, torch::Tensor qkv,
   TORCH_CHECK(dout.is_cuda() && dout.is_contiguous() && qkv.is_contiguous());
   const int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3),
             D = qkv.size(4);
-  QkvStrides st;
-  st.qt = 3L * H * D;
-  st.qb = (long)T * st.qt;
-  st.qh = D;
-  st.ot = (long)H * D;
-  st.ob = (long)T * st.ot;
-  st.oh = D;
+  const QkvStrides st = fused_qkv_strides(T, H, D);
   auto delta = run_rowdot(dout, o, B, H, T, D, st);
 
   auto dqkv = torch::empty_like(qkv);
@@ -1377,47 +988,5 @@ torch::Tensor fmha_bwd_qkv(torch::Tensor dout, torch::Tensor qkv,
       D, launch_fmha_bwd<kD>(a, lse, delta, dbase, dbase + (long)H * D,
                              dbase + 2L * H * D));
   return dqkv;
-}
-
-
-torch::Tensor tr16_probe(long mode) {
-  auto out = torch::zeros({64, 4}, torch::TensorOptions()
-                                       .dtype(torch::kInt16)
-                                       .device(torch::kCUDA));
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(tr16_probe_kernel, dim3(1), dim3(64), 2048, stream,
-                     (unsigned short*)out.data_ptr(), (int)mode);
-  HIP_CHECK_LAST();
-  return out;
-}
-
-torch::Tensor mfma32_probe(torch::Tensor a, torch::Tensor b) {
-  TORCH_CHECK(a.is_cuda() && a.is_contiguous() && a.dim() == 2 &&
-              a.size(0) == 32 && a.size(1) == 16);
-  TORCH_CHECK(b.is_cuda() && b.is_contiguous() && b.dim() == 2 &&
-              b.size(0) == 16 && b.size(1) == 32);
-  TORCH_CHECK(a.scalar_type() == torch::kFloat32 &&
-              b.scalar_type() == torch::kFloat32);
-  auto c = torch::zeros({32, 32}, a.options());
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(mfma32_probe_kernel, dim3(1), dim3(64), 0, stream,
-                     a.data_ptr<float>(), b.data_ptr<float>(),
-                     c.data_ptr<float>());
-  HIP_CHECK_LAST();
-  return c;
-}
-
-torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b) {
-  TORCH_CHECK(a.is_cuda() && a.sizes() == torch::IntArrayRef({16, 32}));
-  TORCH_CHECK(b.is_cuda() && b.sizes() == torch::IntArrayRef({32, 16}));
-  auto a32 = a.to(torch::kFloat32).contiguous();
-  auto b32 = b.to(torch::kFloat32).contiguous();
-  auto c = torch::empty({16, 16}, a32.options());
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(mfma_probe_kernel, dim3(1), dim3(64), 0, stream,
-                     a32.data_ptr<float>(), b32.data_ptr<float>(),
-                     c.data_ptr<float>());
-  HIP_CHECK_LAST();
-  return c;
 }
 #endif  // VITFSDP_KERNELS_ONLY

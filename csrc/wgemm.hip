@@ -9,15 +9,7 @@
 // per thread per K-step.  gfx950's ds_read_b64_tr_b16 removes that
 // entirely: tiles stay row-major in LDS (vectorized 16-B stores straight
 // from the coalesced global loads) and the MFMA fragments are gathered
-// along K by the hardware transpose read.
-//
-// ds_read_b64_tr_b16 semantics (pinned on-device by tr16_probe,
-// tests/test_gpu_kernels.py): per 16-lane group, lane i reads 4
-// contiguous u16 at its own 8-byte-aligned address; the 64 gathered
-// elements form a stream ordered (lane, elem) and lane l receives
-// stream[(l&15) + 16*j], j = 0..3.  Reading a [4 row][16 col] sub-tile
-// with lane addresses row = base+(i>>2), col = colbase+(i&3)*4 therefore
-// delivers column (l&15) of the sub-tile to lane l — a free transpose.
+// along K by the hardware transpose read (semantics: mfma_tiles.h).
 //
 // Tiling: 256x256 C tile per 512-thread block (8 waves as 2m x 4n, each
 // wave 128x64), BK = 64, single-buffered LDS (66.6 KB -> 2 blocks/CU)
@@ -25,19 +17,13 @@
 // before this step's MFMA phases.
 
 #ifndef VITFSDP_KERNELS_ONLY
-#ifndef VITFSDP_KERNELS_ONLY
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
 #endif
-#endif
 
-#include "common.h"
+#include "mfma_tiles.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 constexpr int kBM = 256;
 constexpr int kBN = 256;
@@ -60,13 +46,9 @@ struct WgemmShared {
 __device__ __forceinline__ u32x2 tr_read(unsigned lds_byte_base, int lane15,
                                          int row_base, int col_base,
                                          int row_stride) {
-  const unsigned addr =
-      lds_byte_base +
-      2u * ((unsigned)((row_base + (lane15 >> 2)) * row_stride + col_base +
-                       (lane15 & 3) * 4));
-  u32x2 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:0" : "=v"(v) : "v"(addr));
-  return v;
+  return tr16_read(lds_byte_base +
+                   2u * ((unsigned)((row_base + (lane15 >> 2)) * row_stride +
+                                    col_base + (lane15 & 3) * 4)));
 }
 
 template <bool WITH_BIAS>
@@ -102,9 +84,8 @@ __global__ __launch_bounds__(kThreads, 2) void wgemm_atb_kernel(
   {
     const int nwg = gridDim.x * gridDim.y;
     if ((nwg & 7) == 0) {
-      const int bid = (int)(blockIdx.x + blockIdx.y * gridDim.x);
-      const int cpx = nwg >> 3;
-      const int swz = (bid & 7) * cpx + (bid >> 3);
+      const int swz = xcd_swizzle_m_major(
+          (int)(blockIdx.x + blockIdx.y * gridDim.x), nwg);
       bx = swz % gridDim.x;
       by = swz / gridDim.x;
     }
@@ -196,7 +177,8 @@ __global__ __launch_bounds__(kThreads, 2) void wgemm_atb_kernel(
         }
         if (mi == 0) {
           // first wait also guards the B fragments (issued earlier,
-          // retired in order before af[0])
+          // retired in order before af[0]), which lds_wait's
+          // two-operand signature does not cover
           asm volatile("s_waitcnt lgkmcnt(%[cnt])"
                        : "+v"(af[cur][0]), "+v"(af[cur][1]),
                          "+v"(bf[0][0]), "+v"(bf[0][1]), "+v"(bf[1][0]),
@@ -205,33 +187,16 @@ __global__ __launch_bounds__(kThreads, 2) void wgemm_atb_kernel(
                        : "memory");
           asm volatile("" : "+v"(bf[3][0]), "+v"(bf[3][1]));
         } else if (mi < 7) {
-          asm volatile("s_waitcnt lgkmcnt(%[cnt])"
-                       : "+v"(af[cur][0]), "+v"(af[cur][1])
-                       : [cnt] "i"(2)
-                       : "memory");
+          lds_wait<2>(af[cur][0], af[cur][1]);
         } else {
-          asm volatile("s_waitcnt lgkmcnt(%[cnt])"
-                       : "+v"(af[cur][0]), "+v"(af[cur][1])
-                       : [cnt] "i"(0)
-                       : "memory");
+          lds_wait<0>(af[cur][0], af[cur][1]);
         }
-        union {
-          u32x2 uu[2];
-          bf16x8 v;
-        } ac;
-        ac.uu[0] = af[cur][0];
-        ac.uu[1] = af[cur][1];
+        const bf16x8 a_frag = frag_from(af[cur][0], af[cur][1]);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
-          union {
-            u32x2 uu[2];
-            bf16x8 v;
-          } bc;
-          bc.uu[0] = bf[ni][0];
-          bc.uu[1] = bf[ni][1];
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              ac.v, bc.v, acc[mi][ni], 0, 0, 0);
+              a_frag, frag_from(bf[ni][0], bf[ni][1]), acc[mi][ni], 0, 0, 0);
         }
         __builtin_amdgcn_s_setprio(0);
         if (WITH_BIAS && wn == 0) {
@@ -289,7 +254,6 @@ template __global__ void wgemm_atb_kernel<false>(const short*, const short*,
 }  // namespace
 
 #ifndef VITFSDP_KERNELS_ONLY
-#ifndef VITFSDP_KERNELS_ONLY
 std::vector<torch::Tensor> wgrad_gemm(torch::Tensor a, torch::Tensor b,
                                       bool with_bias) {
   TORCH_CHECK(a.is_cuda() && a.is_contiguous() && b.is_contiguous());
@@ -336,6 +300,4 @@ std::vector<torch::Tensor> wgrad_gemm(torch::Tensor a, torch::Tensor b,
   if (with_bias) return {c, dbias};
   return {c};
 }
-#endif
-
 #endif  // VITFSDP_KERNELS_ONLY

@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "csrc/fmha.hip",
         "csrc/wgemm.hip",
         "csrc/fgemm.hip",
+        "csrc/probes.hip",
     ],
     libraries=["hipblaslt"],
     extra_compile_args={

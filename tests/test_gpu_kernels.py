@@ -44,6 +44,20 @@ def test_mfma_probe_layout():
     )
 
 
+def test_tr16_probe_semantics():
+    """Pin the ds_read_b64_tr_b16 gather that csrc/mfma_tiles.h documents
+    and every transpose-read kernel relies on: within a 16-lane group,
+    lane i reads 4 contiguous u16 at its own address, the 64 elements
+    form a stream ordered (lane, elem), and lane l receives
+    stream[(l & 15) + 16 * j].  The probe fills lds[i] = i."""
+    lane = torch.arange(64).unsqueeze(1)
+    s = (lane & 15) + 16 * torch.arange(4).unsqueeze(0)  # stream index
+    # mode 2: every group reads lane address (i & 15) * 4 -> lds == stream
+    assert torch.equal(EXT.tr16_probe(2).cpu().long(), s)
+    # mode 3: lane address i * 4 -> group g reads lds[64 g ..]
+    assert torch.equal(EXT.tr16_probe(3).cpu().long(), s + 64 * (lane >> 4))
+
+
 @pytest.mark.parametrize("shape", [(128, 256, 5120), (4, 7, 64), (2, 3, 1024)])
 def test_layernorm_fwd_bwd(shape):
     from vit_10b_fsdp_example_amd.ops import layer_norm
@@ -150,6 +164,7 @@ def test_multi_tensor_sqnorm_scale():
         (1, 2, 64, 16),
         (1, 3, 80, 32),    # T not a multiple of the q/k tiles
         (1, 1, 1024, 160), # long sequence (image_size 448 class)
+        (1, 1, 40, 176),   # DP=192 > D: scalar-tail fragment loads
     ],
 )
 def test_fmha_fwd_vs_fp32_reference(B, H, T, D):
@@ -173,7 +188,16 @@ def test_fmha_fwd_vs_fp32_reference(B, H, T, D):
     )
 
 
-@pytest.mark.parametrize("B,H,T,D", [(2, 4, 256, 160), (1, 2, 80, 64)])
+@pytest.mark.parametrize(
+    "B,H,T,D",
+    [
+        (2, 4, 256, 160),
+        (1, 2, 80, 64),
+        # DP > D (scalar-tail fragment loads, staging column guards):
+        (1, 2, 80, 48),    # QSub=2, DP=64, T not a multiple of 32 or 64
+        (1, 1, 40, 176),   # QSub=1, DP=192, one ragged tile
+    ],
+)
 def test_fmha_bwd_vs_fp32_reference(B, H, T, D):
     torch.manual_seed(1)
     q = torch.randn(B, H, T, D, device=_dev(), dtype=torch.bfloat16)
@@ -613,6 +637,7 @@ def test_fwd_gemm_gelu_erf_vs_reference():
         (2, 3, 128, 160),
         (1, 1, 1024, 160),  # long context (448px class)
         (1, 2, 200, 160),   # ragged: T not a tile multiple
+        (1, 2, 80, 48),     # QSub=2 kernels, DP=64 > D
     ],
 )
 def test_fmha_dropout_in_kernel_fwd_bwd(B, H, T, D):
