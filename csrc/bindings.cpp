@@ -55,6 +55,8 @@ torch::Tensor fmha_bwd_qkv(torch::Tensor dout, torch::Tensor qkv,
                            torch::Tensor o, torch::Tensor lse,
                            long num_heads, double scale, double p_drop,
                            long seed);
+torch::Tensor fmha_rowdot(torch::Tensor dout, torch::Tensor o);
+std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x);
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma32_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor tr16_probe(long mode);
@@ -118,6 +120,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dout"), py::arg("qkv"), py::arg("o"), py::arg("lse"),
         py::arg("num_heads"), py::arg("scale"), py::arg("p_drop") = 0.0,
         py::arg("seed") = 0);
+  m.def("fmha_rowdot", &fmha_rowdot,
+        "Delta = rowsum(dO * O) of the attention backward, fp32 [B,H,T], "
+        "for contiguous [B,H,T,D] operands",
+        py::arg("dout"), py::arg("o"));
+  m.def("gelu_bwd_colsum", &gelu_bwd_colsum,
+        "(dx, colsum): exact-erf GELU backward and the bf16 column sums "
+        "of dx over all rows (fc1 bias gradient) in one pass",
+        py::arg("dy"), py::arg("x"));
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("mfma32_probe", &mfma32_probe, "32x32x16 bf16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 semantics probe");

@@ -660,9 +660,96 @@ __global__ __launch_bounds__(kBlockThreads, 2) void fmha_bwd_dkv_kernel(
   }
 }
 
-// Delta = rowsum(dO * O): one wave per (b,h,t) row; o/dO are strided
-// [B,T,H,D]-layout tensors, delta is contiguous [B,H,T]
-__global__ __launch_bounds__(64) void fmha_rowdot_kernel(
+// Delta = rowsum(dO * O), bandwidth-bound: it streams dO and O once
+// (671 MB at the ViT-10B shape) for 4 MB of output.  o/dO are strided
+// [B,T,H,D]- or [B,H,T,D]-layout tensors, delta is contiguous [B,H,T].
+//
+// Deliberately NOT fused into fmha_bwd_dq_kernel, which loads the same
+// dO rows: that kernel sits exactly on an occupancy step (168 VGPRs,
+// 3 waves/SIMD, profiles/raw/kernel_resources.txt) and has no registers
+// left for the O fragments.
+//
+// 256-thread blocks, 8 lanes per row (32 rows per block iteration,
+// grid-stride), 16-byte loads: lane g of a row's group loads vectors
+// g, g+8, g+16 (D <= 192 is at most 24 vectors).  Rows are walked in
+// MEMORY order (h fastest when the head stride is the smaller one, as in
+// the [B,T,H,D] training layout), so a wave reads 8 adjacent rows as
+// one contiguous span instead of 8 pieces a token stride apart.
+//
+// Summation order: element e of a row lands in accumulator j = e % 8 of
+// lane g = (e / 8) % 8, i.e. "virtual lane" 8g + j = e % 64 — the lane
+// the one-wave-per-row kernel below gives it — and the reduction
+// replays that kernel's xor butterfly (32, 16, 8 across the 8 lanes,
+// then 4, 2, 1 across the accumulators).  fp32 addition is commutative,
+// so delta, and with it dq/dk/dv, is bit-identical to the scalar path.
+constexpr int kRowdotLanes = 8;
+constexpr int kRowdotRows = kBlockThreads / kRowdotLanes;  // per iteration
+constexpr int kRowdotMaxLoads = kMaxD / 8 / kRowdotLanes;  // 3
+
+__global__ __launch_bounds__(kBlockThreads) void fmha_rowdot_kernel(
+    const ushort8_t* __restrict__ dout, const ushort8_t* __restrict__ o,
+    float* __restrict__ delta, int n_rows, int T, int H, int nvec,
+    long sob, long soh, long sot /* strides in 8-element vectors */,
+    int h_fast) {
+  const int g = threadIdx.x % kRowdotLanes;
+  const int slot = threadIdx.x / kRowdotLanes;
+  for (long r0 = (long)blockIdx.x * kRowdotRows; r0 < n_rows;
+       r0 += (long)gridDim.x * kRowdotRows) {
+    const bool ok = r0 + slot < n_rows;
+    // every lane stays in the loop for the shuffles; rows past the end
+    // load nothing and store nothing
+    const unsigned r = ok ? (unsigned)(r0 + slot) : 0u;
+    unsigned b, h, t;
+    if (h_fast) {
+      h = r % (unsigned)H;
+      t = (r / (unsigned)H) % (unsigned)T;
+    } else {
+      t = r % (unsigned)T;
+      h = (r / (unsigned)T) % (unsigned)H;
+    }
+    b = r / ((unsigned)T * (unsigned)H);
+    const long base = (long)b * sob + (long)h * soh + (long)t * sot;
+
+    ushort8_t dv[kRowdotMaxLoads], ov[kRowdotMaxLoads];
+#pragma unroll
+    for (int k = 0; k < kRowdotMaxLoads; ++k) {
+      const int v = g + k * kRowdotLanes;
+      if (ok && v < nvec) {
+        dv[k] = dout[base + v];
+        ov[k] = o[base + v];
+      }
+    }
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < kRowdotMaxLoads; ++k) {
+      const int v = g + k * kRowdotLanes;
+      if (ok && v < nvec) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          acc[j] += bf16_to_f32(dv[k][j]) * bf16_to_f32(ov[k][j]);
+      }
+    }
+    // virtual-lane offsets 32, 16, 8 = lane-group offsets 4, 2, 1
+#pragma unroll
+    for (int off = kRowdotLanes / 2; off > 0; off >>= 1) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], off);
+    }
+    // virtual-lane offsets 4, 2, 1 stay inside the lane
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] += acc[j + 4];
+    acc[0] += acc[2];
+    acc[1] += acc[3];
+    acc[0] += acc[1];
+    if (ok && g == 0) delta[((long)b * H + h) * T + t] = acc[0];
+  }
+}
+
+// Scalar path for operands whose base address is not 16-byte aligned:
+// one wave per (b,h,t) row, 2-byte loads.
+__global__ __launch_bounds__(64) void fmha_rowdot_scalar_kernel(
     const unsigned short* __restrict__ dout,
     const unsigned short* __restrict__ o, float* __restrict__ delta, int T,
     int H, int D, long sob, long soh, long sot) {
@@ -861,10 +948,33 @@ torch::Tensor run_rowdot(const torch::Tensor& dout, const torch::Tensor& o,
                          int B, int H, int T, int D, const QkvStrides& st) {
   auto delta = torch::empty({B, H, T}, dout.options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(fmha_rowdot_kernel, dim3((long)B * H * T), dim3(64), 0,
-                     stream, (const unsigned short*)dout.data_ptr(),
-                     (const unsigned short*)o.data_ptr(),
-                     delta.data_ptr<float>(), T, H, D, st.ob, st.oh, st.ot);
+  const long n_rows = (long)B * H * T;
+  if (n_rows == 0) return delta;
+  // 16-byte loads need 16-byte-aligned bases (D % 16 == 0 makes every
+  // stride a multiple of 8 elements already); the row index is split
+  // with 32-bit divides
+  const bool aligned =
+      ((reinterpret_cast<uintptr_t>(dout.data_ptr()) |
+        reinterpret_cast<uintptr_t>(o.data_ptr())) & 15) == 0 &&
+      D % 8 == 0 && D <= kMaxD && st.ob % 8 == 0 && st.oh % 8 == 0 &&
+      st.ot % 8 == 0;
+  if (aligned && n_rows < (1L << 31)) {
+    // 2048 blocks = 256 CUs x 8: one block per SIMD slot at full
+    // occupancy (the kernel needs well under 64 VGPRs)
+    const long n_blocks =
+        std::min<long>((n_rows + kRowdotRows - 1) / kRowdotRows, 2048);
+    hipLaunchKernelGGL(fmha_rowdot_kernel, dim3((unsigned)n_blocks),
+                       dim3(kBlockThreads), 0, stream,
+                       (const ushort8_t*)dout.data_ptr(),
+                       (const ushort8_t*)o.data_ptr(), delta.data_ptr<float>(),
+                       (int)n_rows, T, H, D / 8, st.ob / 8, st.oh / 8,
+                       st.ot / 8, st.oh < st.ot ? 1 : 0);
+  } else {
+    hipLaunchKernelGGL(fmha_rowdot_scalar_kernel, dim3(n_rows), dim3(64), 0,
+                       stream, (const unsigned short*)dout.data_ptr(),
+                       (const unsigned short*)o.data_ptr(),
+                       delta.data_ptr<float>(), T, H, D, st.ob, st.oh, st.ot);
+  }
   HIP_CHECK_LAST();
   return delta;
 }
@@ -939,6 +1049,23 @@ std::vector<torch::Tensor> fmha_bwd(torch::Tensor dout, torch::Tensor q,
       D, launch_fmha_bwd<kD>(a, lse, delta, (short*)dq.data_ptr(),
                              (short*)dk.data_ptr(), (short*)dv.data_ptr()));
   return {dq, dk, dv};
+}
+
+// Delta alone, for contiguous [B,H,T,D] operands (direct kernel tests)
+torch::Tensor fmha_rowdot(torch::Tensor dout, torch::Tensor o) {
+  TORCH_CHECK(dout.is_cuda() && o.is_cuda() && dout.is_contiguous() &&
+                  o.is_contiguous(),
+              "fmha_rowdot: contiguous GPU tensors");
+  TORCH_CHECK(dout.scalar_type() == torch::kBFloat16 &&
+                  o.scalar_type() == torch::kBFloat16,
+              "fmha_rowdot: bf16 only");
+  TORCH_CHECK(dout.dim() == 4 && dout.sizes() == o.sizes(),
+              "fmha_rowdot: two [B, H, T, D] tensors of one shape");
+  const int B = dout.size(0), H = dout.size(1), T = dout.size(2),
+            D = dout.size(3);
+  TORCH_CHECK(D % 16 == 0 && D <= kMaxD,
+              "fmha_rowdot: head_dim must be a multiple of 16 and <= ", kMaxD);
+  return run_rowdot(dout, o, B, H, T, D, contiguous_strides(H, T, D));
 }
 
 // ---- fused-qkv API: zero-copy path used by the Attention module ----

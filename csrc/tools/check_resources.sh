@@ -1,14 +1,15 @@
 #!/bin/bash
 # Per-kernel register/scratch/occupancy table from the compiler's
 # resource remarks (plain kernels-only compile, no torch headers):
-#   bash csrc/tools/check_resources.sh                # all MFMA TUs
+#   bash csrc/tools/check_resources.sh                # all kernel TUs
 #   bash csrc/tools/check_resources.sh csrc/fmha.hip  # one file
 # Compare against profiles/raw/kernel_resources.txt before merging a
 # change to these kernels: they sit on occupancy steps.
 set -e -o pipefail
 cd "$(dirname "$0")/../.."
 if [ $# -gt 0 ]; then SRCS=("$@"); else
-  SRCS=(csrc/fmha.hip csrc/wgemm.hip csrc/fgemm.hip csrc/probes.hip)
+  SRCS=(csrc/fmha.hip csrc/wgemm.hip csrc/fgemm.hip csrc/probes.hip
+        csrc/layernorm.hip csrc/gelu.hip)
 fi
 OUT=$(mktemp -d)
 trap 'rm -rf "$OUT"' EXIT

@@ -23,6 +23,7 @@ ext = CUDAExtension(
         "csrc/adamw.hip",
         "csrc/cross_entropy.hip",
         "csrc/fmha.hip",
+        "csrc/gelu.hip",
         "csrc/wgemm.hip",
         "csrc/fgemm.hip",
         "csrc/probes.hip",

@@ -267,6 +267,28 @@ def _gelu_fusion_on():
     )
 
 
+# --------------------------------------------------------------------------
+# GELU backward with the fc1 bias gradient in the same pass
+# (csrc/gelu.hip).  In the stock backward of linear -> gelu, GeluBackward
+# writes dgelu [.., hid] and AddmmBackward then reads all of it again
+# for the bias gradient:
+#     gelu_backward(grad [B, T, hid], pre [B, T, hid]) -> dx
+#     view(dx, [B*T, hid])
+#     mm(dx2d, W) ; mm(dx2d.t(), x2d)
+#     sum.dim_IntList(dx2d, [0], keepdim=True) -> [1, hid] -> view [hid]
+# (sequence confirmed with a logging dispatch mode).  The hook answers
+# the gelu_backward with _C.gelu_bwd_colsum, parks the column sums, and
+# answers that sum from them.  On by default once the MLP dims are
+# configured; VITFSDP_FUSED_DGELU_DBIAS=0 turns it off.
+# --------------------------------------------------------------------------
+
+
+def _dgelu_dbias_on():
+    return (
+        os.environ.get("VITFSDP_FUSED_DGELU_DBIAS", "1") != "0"
+        and _GELU_CFG["hid"] > 0
+    )
+
 
 
 class TunedGemmMode(TorchDispatchMode):
@@ -282,7 +304,8 @@ class TunedGemmMode(TorchDispatchMode):
     the whole step (push around forward AND backward).
     """
 
-    def __init__(self, table=None, native_wgrad=None, handler=None):
+    def __init__(self, table=None, native_wgrad=None, handler=None,
+                 dgelu_handler=None):
         super().__init__()
         self.table = lt_algo_table() if table is None else table
         self.native_wgrad = (
@@ -295,8 +318,25 @@ class TunedGemmMode(TorchDispatchMode):
         self.wgrad_hits = 0
         # fused-GELU state (see module comment above):
         self.fused_gelu = _gelu_fusion_on()
-        self._pending_gelu = {}  # pre-act data_ptr -> gelu_out (transient)
+        # pre-act data_ptr -> (pre-act, gelu_out), transient.  The entry
+        # holds the pre-activation itself so its address cannot be freed
+        # and handed to another tensor while the key is live.
+        self._pending_gelu = {}
         self.gelu_hits = 0
+        # fused dgelu + fc1 bias gradient (see module comment above).
+        # test seam: dgelu_handler(dy, x) -> (dx, colsum) replaces
+        # _C.gelu_bwd_colsum and lifts the CUDA/bf16 gate
+        self._dgelu_handler = dgelu_handler
+        self.fused_dgelu = _dgelu_dbias_on() and (
+            dgelu_handler is not None or self._handler is None
+        )
+        self._dgelu_stash = None  # (dx, colsum): at most one entry
+        self.dgelu_hits = 0
+        self.dbias_hits = 0
+
+    def __exit__(self, exc_type, exc_val, exc_tb):
+        self._dgelu_stash = None
+        return super().__exit__(exc_type, exc_val, exc_tb)
 
     def _tuned_index(self, a, b):
         if not self.table:
@@ -346,8 +386,72 @@ class TunedGemmMode(TorchDispatchMode):
         self.gelu_hits += 1
         if len(self._pending_gelu) > 4:  # unconsumed strays (shouldn't happen)
             self._pending_gelu.clear()
-        self._pending_gelu[pre.data_ptr()] = out
+        self._pending_gelu[pre.data_ptr()] = (pre, out)
         return pre
+
+    # -- fused dgelu + bias-gradient helpers --------------------------------
+
+    def _is_mlp_dgelu(self, args, kwargs):
+        if len(args) != 2 or kwargs.get("approximate", "none") != "none":
+            return False
+        dy, x = args
+        if not (
+            dy.dim() >= 2
+            and dy.shape[-1] == _GELU_CFG["hid"]
+            and dy.shape == x.shape
+            and dy.is_contiguous() and x.is_contiguous()
+        ):
+            return False
+        if self._dgelu_handler is not None:
+            return True
+        return (
+            dy.is_cuda and dy.dtype == torch.bfloat16
+            and x.dtype == torch.bfloat16
+            and dy.shape[-1] % 8 == 0
+            and use_hip(dy)
+        )
+
+    def _fused_dgelu(self, dy, x):
+        if self._dgelu_handler is not None:
+            dx, colsum = self._dgelu_handler(dy, x)
+        else:
+            # a missing kernel is an error here, not a fallback
+            dx, colsum = ext().gelu_bwd_colsum(dy, x)
+        self.dgelu_hits += 1
+        # holding dx keeps its address from being recycled while the
+        # entry lives; the next gelu_backward overwrites it
+        self._dgelu_stash = (dx, colsum)
+        return dx
+
+    def _stashed_dbias(self, args, kwargs):
+        """The parked column sums if this sum is dx.sum over every dim
+        but the last, else None."""
+        if self._dgelu_stash is None or kwargs.get("dtype") is not None:
+            return None
+        dx, colsum = self._dgelu_stash
+        t = args[0]
+        dims = args[1] if len(args) > 1 else None
+        keepdim = args[2] if len(args) > 2 else kwargs.get("keepdim", False)
+        if not (
+            isinstance(t, torch.Tensor)
+            and dims is not None
+            and t.dtype == dx.dtype
+            and t.device == dx.device
+            and t.untyped_storage().data_ptr()
+            == dx.untyped_storage().data_ptr()
+            and t.storage_offset() == dx.storage_offset()
+            and t.numel() == dx.numel()
+            and t.dim() >= 2
+            and t.shape[-1] == dx.shape[-1]
+            and t.is_contiguous()
+            and sorted(d % t.dim() for d in dims) == list(range(t.dim() - 1))
+        ):
+            return None
+        self._dgelu_stash = None
+        self.dbias_hits += 1
+        if keepdim:
+            return colsum.view([1] * (t.dim() - 1) + [t.shape[-1]])
+        return colsum
 
     def __torch_dispatch__(self, func, types, args=(), kwargs=None):
         kwargs = kwargs or {}
@@ -389,8 +493,18 @@ class TunedGemmMode(TorchDispatchMode):
                 self.hits += 1
                 return self._route(a, b, idx, bias)
         elif self.fused_gelu and func is torch.ops.aten.gelu.default:
-            out = self._pending_gelu.pop(args[0].data_ptr(), None)
+            _, out = self._pending_gelu.pop(args[0].data_ptr(), (None, None))
             if out is not None and out.shape == args[0].shape:
+                return out
+        elif self.fused_dgelu and func is torch.ops.aten.gelu_backward.default:
+            if self._is_mlp_dgelu(args, kwargs):
+                return self._fused_dgelu(*args)
+        elif (
+            self._dgelu_stash is not None
+            and func is torch.ops.aten.sum.dim_IntList
+        ):
+            out = self._stashed_dbias(args, kwargs)
+            if out is not None:
                 return out
         return func(*args, **kwargs)
 
@@ -398,9 +512,10 @@ class TunedGemmMode(TorchDispatchMode):
 def gemm_dispatch_context():
     """Context manager for the training step (forward and backward):
     activates the dispatcher-level GEMM rerouting when the tuned
-    algorithm table is present, fused MLP GELU is configured, or
-    VITFSDP_NATIVE_WGRAD=2; otherwise a no-op."""
-    if lt_algo_table() or _gelu_fusion_on():
+    algorithm table is present, fused MLP GELU or the fused
+    dgelu + bias-gradient pass is configured, or VITFSDP_NATIVE_WGRAD=2;
+    otherwise a no-op."""
+    if lt_algo_table() or _gelu_fusion_on() or _dgelu_dbias_on():
         return TunedGemmMode()
     if _NATIVE_WGRAD_DISPATCH:
         return NativeWgradMode()  # backward-compatible, wgrad only
