@@ -979,6 +979,37 @@ torch::Tensor run_rowdot(const torch::Tensor& dout, const torch::Tensor& o,
   return delta;
 }
 
+bool supported_head_dim(long D) { return D >= 16 && D <= kMaxD && D % 16 == 0; }
+
+// The backward kernels read every operand through raw pointers with
+// strides derived from q's (or qkv's) shape alone, so each one has to be
+// exactly the tensor the strides describe: a view with other strides
+// gives wrong gradients, a smaller one an out-of-bounds read.
+void check_bwd_operand(const char* fn, const char* name,
+                       const torch::Tensor& t, const torch::Tensor& like,
+                       at::IntArrayRef shape) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device(), fn, ": ", name,
+              " must be a GPU tensor on the device of the other operands");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, fn, ": ", name,
+              " must be bf16, got ", t.scalar_type());
+  TORCH_CHECK(t.sizes() == shape, fn, ": ", name, " must have shape ", shape,
+              ", got ", t.sizes());
+  TORCH_CHECK(t.is_contiguous(), fn, ": ", name, " must be contiguous");
+}
+
+void check_bwd_lse(const char* fn, const torch::Tensor& lse,
+                   const torch::Tensor& like, long B, long H, long T) {
+  TORCH_CHECK(lse.is_cuda() && lse.device() == like.device(), fn,
+              ": lse must be a GPU tensor on the device of the other operands");
+  TORCH_CHECK(lse.scalar_type() == torch::kFloat32, fn,
+              ": lse must be fp32, got ", lse.scalar_type());
+  TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H &&
+                  lse.size(2) == T,
+              fn, ": lse must have shape [B, H, T] = [", B, ", ", H, ", ", T,
+              "], got ", lse.sizes());
+  TORCH_CHECK(lse.is_contiguous(), fn, ": lse must be contiguous");
+}
+
 }  // namespace
 
 // ---- [B,H,T,D] contiguous API (kernel unit tests, generic use) ----
@@ -1008,7 +1039,17 @@ std::vector<torch::Tensor> fmha_bwd(torch::Tensor dout, torch::Tensor q,
                                     torch::Tensor k, torch::Tensor v,
                                     torch::Tensor o, torch::Tensor lse,
                                     double scale, double p_drop, long seed) {
-  TORCH_CHECK(dout.is_cuda() && dout.is_contiguous());
+  TORCH_CHECK(q.is_cuda() && q.dim() == 4,
+              "fmha_bwd: q must be a GPU tensor [B, H, T, D]");
+  TORCH_CHECK(supported_head_dim(q.size(3)),
+              "fmha_bwd: head_dim must be a multiple of 16 and <= ", kMaxD,
+              ", got ", q.size(3));
+  check_bwd_operand("fmha_bwd", "q", q, q, q.sizes());
+  check_bwd_operand("fmha_bwd", "k", k, q, q.sizes());
+  check_bwd_operand("fmha_bwd", "v", v, q, q.sizes());
+  check_bwd_operand("fmha_bwd", "o", o, q, q.sizes());
+  check_bwd_operand("fmha_bwd", "dout", dout, q, q.sizes());
+  check_bwd_lse("fmha_bwd", lse, q, q.size(0), q.size(1), q.size(2));
   const int B = q.size(0), H = q.size(1), T = q.size(2), D = q.size(3);
   const QkvStrides st = contiguous_strides(H, T, D);
   auto delta = run_rowdot(dout, o, B, H, T, D, st);
@@ -1099,7 +1140,26 @@ torch::Tensor fmha_bwd_qkv(torch::Tensor dout, torch::Tensor qkv,
                            torch::Tensor o, torch::Tensor lse,
                            long num_heads, double scale, double p_drop,
                            long seed) {
-  TORCH_CHECK(dout.is_cuda() && dout.is_contiguous() && qkv.is_contiguous());
+  TORCH_CHECK(qkv.is_cuda() && qkv.is_contiguous() && qkv.dim() == 5 &&
+                  qkv.size(2) == 3 && qkv.size(3) == num_heads,
+              "fmha_bwd_qkv: expected contiguous GPU qkv [B, T, 3, H, D]");
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16,
+              "fmha_bwd_qkv: qkv must be bf16, got ", qkv.scalar_type());
+  TORCH_CHECK(supported_head_dim(qkv.size(4)),
+              "fmha_bwd_qkv: head_dim must be a multiple of 16 and <= ", kMaxD,
+              ", got ", qkv.size(4));
+  {
+    // o and dO are [B, T, H*D]; the equivalent [B, T, H, D] view is
+    // accepted too (same memory)
+    const long b = qkv.size(0), t = qkv.size(1), h = qkv.size(3),
+               d = qkv.size(4);
+    const std::vector<long> flat{b, t, h * d}, split{b, t, h, d};
+    check_bwd_operand("fmha_bwd_qkv", "o", o, qkv,
+                      o.dim() == 4 ? split : flat);
+    check_bwd_operand("fmha_bwd_qkv", "dout", dout, qkv,
+                      dout.dim() == 4 ? split : flat);
+    check_bwd_lse("fmha_bwd_qkv", lse, qkv, b, h, t);
+  }
   const int B = qkv.size(0), T = qkv.size(1), H = qkv.size(3),
             D = qkv.size(4);
   const QkvStrides st = fused_qkv_strides(T, H, D);

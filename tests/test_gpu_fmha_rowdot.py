@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.fmha_reference import check_kernel_outputs
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -88,6 +90,10 @@ def test_fmha_bwd_with_new_rowdot(B, H, T, D):
     for got, ref in ((dv, rv), (dq, rq), (dk, rk)):
         np.testing.assert_allclose(got.float().cpu().numpy(),
                                    ref.cpu().numpy(), rtol=0.1, atol=0.06)
+    check_kernel_outputs(
+        q, k, v, do, scale,
+        {"o": o, "lse": lse, "dq": dq, "dk": dk, "dv": dv},
+        f"rowdot-bwd/T{T}/D{D}")
 
 
 @pytest.mark.parametrize("B,H,T,D", [(1, 2, 80, 48), (2, 4, 256, 160)])
@@ -107,3 +113,8 @@ def test_fmha_bwd_qkv_with_new_rowdot(B, H, T, D):
     ref = torch.stack([rq, rk, rv], 0).permute(1, 3, 0, 2, 4)  # [B,T,3,H,D]
     np.testing.assert_allclose(dqkv.float().cpu().numpy(), ref.cpu().numpy(),
                                rtol=0.1, atol=0.06)
+    dq, dk, dv = dqkv.permute(2, 0, 3, 1, 4).unbind(0)
+    check_kernel_outputs(
+        q, k, v, do_bhtd, scale,
+        {"o": o.view(B, T, H, D).transpose(1, 2), "lse": lse, "dq": dq,
+         "dk": dk, "dv": dv}, f"rowdot-bwd-qkv/T{T}/D{D}")

@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.fmha_reference import check_kernel_outputs, keep_mask
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -186,6 +188,10 @@ def test_fmha_fwd_vs_fp32_reference(B, H, T, D):
     np.testing.assert_allclose(
         lse.cpu().numpy(), ref_lse.cpu().numpy(), rtol=1e-3, atol=1e-2
     )
+    # and against fp64 with the rounding-model bound (forward only: the
+    # upstream gradient does not enter o or lse)
+    check_kernel_outputs(q, k, v, torch.zeros_like(q), scale,
+                         {"o": o, "lse": lse}, f"fwd/T{T}/D{D}")
 
 
 @pytest.mark.parametrize(
@@ -224,6 +230,9 @@ def test_fmha_bwd_vs_fp32_reference(B, H, T, D):
     np.testing.assert_allclose(
         dk.float().cpu().numpy(), kf.grad.cpu().numpy(), rtol=0.1, atol=0.06
     )
+    check_kernel_outputs(
+        q, k, v, do, scale,
+        {"o": o, "lse": lse, "dq": dq, "dk": dk, "dv": dv}, f"bwd/T{T}/D{D}")
 
 
 def test_attention_autograd_path():
@@ -279,6 +288,12 @@ def test_fmha_qkv_fused_path():
         qkv.grad.float().cpu().numpy(), qf.grad.cpu().numpy(),
         rtol=0.1, atol=0.06,
     )
+    qd, kd, vd = qkv.detach().permute(2, 0, 3, 1, 4).unbind(0)
+    dq, dk, dv = qkv.grad.permute(2, 0, 3, 1, 4).unbind(0)
+    check_kernel_outputs(
+        qd, kd, vd, do.view(B, T, H, D).transpose(1, 2), D ** -0.5,
+        {"o": o.detach().view(B, T, H, D).transpose(1, 2), "dq": dq,
+         "dk": dk, "dv": dv}, "qkv-fused")
 
 
 def test_fused_add_layernorm():
@@ -693,6 +708,10 @@ def test_fmha_dropout_in_kernel_fwd_bwd(B, H, T, D):
                            (dv, vf.grad, "dv")]:
         rel = (got.float() - ref).abs().max() / (ref.abs().max() + 1e-6)
         assert float(rel) < 6e-2, (name, float(rel))
+    check_kernel_outputs(
+        q.detach(), k.detach(), v.detach(), do, scale,
+        {"o": o, "lse": lse, "dq": dq, "dk": dk, "dv": dv},
+        f"dropout/T{T}/D{D}", keep_mask(seed, p, B, H, T, _dev()), p)
 
 
 def test_attention_dropout_autograd_path():

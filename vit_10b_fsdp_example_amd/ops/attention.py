@@ -79,16 +79,22 @@ class _FlashAttentionFn(torch.autograd.Function):
         return dq, dk, dv, None, None, None
 
 
+def _kernel_dtype(dtype):
+    """The flash kernels are bf16-only (fmha_fwd refuses anything else);
+    every other dtype, fp16 included, takes the math composition."""
+    return dtype == torch.bfloat16
+
+
 def attention(q, k, v, scale=None, dropout_p=0.0, training=False):
     """Attention core on [B, H, T, D] tensors.
 
-    GPU: our flash-style HIP kernel, attention dropout in-kernel.
-    CPU: math composition.
+    GPU bf16: our flash-style HIP kernel, attention dropout in-kernel.
+    CPU, and GPU dtypes other than bf16: math composition.
     """
     if scale is None:
         scale = q.shape[-1] ** -0.5
     use_kernel = (
-        q.dtype in (torch.bfloat16, torch.float16)
+        _kernel_dtype(q.dtype)
         and use_hip(q, k, v)
         and hasattr(ext(), "fmha_fwd")
     )
@@ -140,7 +146,7 @@ def attention_qkv(qkv, num_heads, scale=None, dropout_p=0.0, training=False):
     if scale is None:
         scale = D ** -0.5
     use_kernel = (
-        qkv.dtype in (torch.bfloat16,)
+        _kernel_dtype(qkv.dtype)
         and use_hip(qkv)
         and hasattr(ext(), "fmha_fwd_qkv")
     )
