@@ -43,6 +43,18 @@ __device__ __forceinline__ u32x2 tr16_read(unsigned lds_byte_addr) {
   return v;
 }
 
+// same, at lds_byte_addr + OFF with OFF (< 64 KB) in the instruction's
+// immediate: reads that differ by a constant share one address VGPR
+template <int OFF>
+__device__ __forceinline__ u32x2 tr16_read_at(unsigned lds_byte_addr) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds offset field is 16 bits");
+  u32x2 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+               : "=v"(v)
+               : "v"(lds_byte_addr), "n"(OFF));
+  return v;
+}
+
 // counted LDS wait: at most N LDS reads still in flight.  The fragment
 // halves about to be consumed ride along as "+v" operands so their
 // MFMAs cannot be scheduled above the wait (guide rule 18) without
@@ -200,4 +212,42 @@ struct TileStage {
 // co-resident blocks share operand panels in its private L2.
 __device__ __forceinline__ int xcd_swizzle_m_major(int bid, int nwg) {
   return (bid & 7) * (nwg >> 3) + (bid >> 3);
+}
+
+// XCD-aware 2D tile clustering for a gridDim.x x gridDim.y grid of
+// output tiles (wgemm.hip, fgemm.hip): the dispatcher places block bid
+// on XCD bid%8, so each XCD's co-resident ~32 workgroups are
+// cid = bid>>3 consecutive.  Give each XCD a contiguous 2D
+// sub-rectangle of the tile grid and walk it in GROUP_M-wide bands:
+// the resident set then covers a GM x (32/GM) RECTANGLE, reusing x
+// panels GM-fold and y panels (32/GM)-fold in the XCD's private L2.
+// (An M-major run reuses only one operand; at 1 workgroup/CU the other
+// operand's streams alone exceed the per-CU HBM budget — MfmaUtil
+// measured 44% on fgemm.)  Grids the 8 sub-rectangles do not divide
+// fall back to the M-major run, tile counts that are no multiple of 8
+// keep the identity mapping.
+__device__ __forceinline__ void xcd_cluster_tile(int& bx, int& by) {
+  bx = blockIdx.x;
+  by = blockIdx.y;
+  const int gx = gridDim.x, gy = gridDim.y;
+  const int nwg = gx * gy;
+  const int bid = (int)(blockIdx.x + blockIdx.y * gx);
+  int sx = 2, sy = 4;  // 8 XCD sub-rectangles
+  if (gy % 4 != 0) {
+    if (gy % 2 == 0) { sx = 4; sy = 2; }
+    else { sx = 8; sy = 1; }
+  }
+  if ((nwg & 7) == 0 && gx % sx == 0 && gy % sy == 0) {
+    const int xcd = bid & 7, cid = bid >> 3;
+    const int lw = gx / sx, lh = gy / sy;
+    const int gm = (lw % 4 == 0) ? 4 : ((lw % 2 == 0) ? 2 : 1);
+    const int per_band = gm * lh;
+    const int band = cid / per_band, r = cid % per_band;
+    bx = (xcd % sx) * lw + band * gm + (r % gm);
+    by = (xcd / sx) * lh + r / gm;
+  } else if ((nwg & 7) == 0) {
+    const int swz = xcd_swizzle_m_major(bid, nwg);
+    bx = swz % gx;
+    by = swz / gx;
+  }
 }

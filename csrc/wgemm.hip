@@ -7,14 +7,40 @@
 // the contraction dim K is the non-contiguous axis of both operands; the
 // usual fix (transpose during LDS staging) costs 64 scalar LDS writes
 // per thread per K-step.  gfx950's ds_read_b64_tr_b16 removes that
-// entirely: tiles stay row-major in LDS (vectorized 16-B stores straight
-// from the coalesced global loads) and the MFMA fragments are gathered
-// along K by the hardware transpose read (semantics: mfma_tiles.h).
+// entirely: tiles stay row-major [k][m] in LDS and the MFMA fragments
+// are gathered along K by the hardware transpose read (semantics:
+// mfma_tiles.h).
 //
 // Tiling: 256x256 C tile per 512-thread block (8 waves as 2m x 4n, each
-// wave 128x64), BK = 64, single-buffered LDS (66.6 KB -> 2 blocks/CU)
-// with T14 register staging: the next K-step's global loads are issued
-// before this step's MFMA phases.
+// wave 128x64), BK = 64, two LDS buffers of 2 x 32 KB = 128 KB, so ONE
+// workgroup per CU.  Structure (the fgemm.hip ladder, profiles/
+// PROFILES.md "wgemm NT ladder"):
+//  * XCD-clustered 2-D tile mapping (xcd_cluster_tile, mfma_tiles.h);
+//  * direct-to-LDS staging: the next K-step's global_load_lds (16 B)
+//    are issued at the top of this step and fly under its MFMAs — no
+//    staging registers, no LDS write pass;
+//  * fragment reads as before (B up front, A through a 2-deep ring of
+//    counted waits), now one address register per fragment plus
+//    immediate offsets.
+// The fragment-to-k mapping and the order of the k-chunk accumulation
+// are those of the register-staged first version: outputs are
+// bit-identical to it.
+//
+// LDS image.  One wave-wide global_load_lds deposits 1 KB contiguously
+// = two packed 512-byte k-rows, so rows cannot be padded; bank spread
+// comes from an XOR applied to the global SOURCE column and to the read
+// address alike.  A 32-lane half of a transpose read (the unit that
+// conflicts) takes 8 k-rows, r..r+3 and r+8..r+11 (r % 16 in {0, 4}),
+// 32 bytes each at ONE 32-byte column chunk; with a 512-byte stride all
+// 8 would sit on the same 32-byte slot of the 256-byte bank row (8-way).
+// Storing chunk c of k-row k at chunk c ^ x(k),
+//     x(k) = (k & 3) | (((k >> 3) & 1) << 2),
+// gives the 8 rows the 8 distinct values of x, hence 8 distinct slots:
+// conflict-free.  The XOR moves whole 32-byte chunks, so every lane's
+// 8-byte address stays aligned and the two 16-byte halves of a chunk
+// keep their order.  For the reading lane x is a lane constant
+// ((col >> 2) | ((seg & 1) << 2)): all reads of a K-step are one
+// address register per 16-column fragment plus an immediate offset.
 
 #ifndef VITFSDP_KERNELS_ONLY
 #include <ATen/cuda/CUDAContext.h>
@@ -29,30 +55,27 @@ constexpr int kBM = 256;
 constexpr int kBN = 256;
 constexpr int kBK = 64;
 constexpr int kThreads = 512;  // 8 waves: 2 (m) x 4 (n)
-// row stride of the LDS tiles in elements: 272 keeps every tr-read lane
-// address 8-byte aligned AND makes the 16-lane transpose-read groups
-// bank-conflict-free (row step = 136 dwords = 8 mod 64, column slots
-// 2 dwords apart: banks 8a+2b are distinct for a,b in 0..3)
-constexpr int kSA = kBM + 16;
-constexpr int kSB = kBN + 16;
+static_assert(kBM == kBN, "one staging/read scheme serves both tiles");
+constexpr int kRowBytes = kBM * 2;  // packed k-row: 512 B = 16 chunks
 
 struct WgemmShared {
-  short a_tile[2][kBK][kSA];  // dY tile, row-major [k][m], double-buffered
-  short b_tile[2][kBK][kSB];  // X  tile, row-major [k][n], double-buffered
+  short a_tile[2][kBK][kBM];  // dY tile, [k][m ^ swizzle], double-buffered
+  short b_tile[2][kBK][kBN];  // X  tile, [k][n ^ swizzle], double-buffered
 };
 
-// one hardware transpose read: returns 4 u16 along rows base..base+3 of
-// a row-major LDS tile at column (colbase + (lane&15))
-__device__ __forceinline__ u32x2 tr_read(unsigned lds_byte_base, int lane15,
-                                         int row_base, int col_base,
-                                         int row_stride) {
-  return tr16_read(lds_byte_base +
-                   2u * ((unsigned)((row_base + (lane15 >> 2)) * row_stride +
-                                    col_base + (lane15 & 3) * 4)));
+// 32-byte chunk XOR of k-row k (header comment)
+__device__ __forceinline__ int chunk_xor(int k) {
+  return (k & 3) | (((k >> 3) & 1) << 2);
+}
+
+__device__ __forceinline__ void glds16(const short* gsrc, short* lds_dst) {
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) void*)gsrc,
+      (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
 }
 
 template <bool WITH_BIAS>
-__global__ __launch_bounds__(kThreads, 2) void wgemm_atb_kernel(
+__global__ __launch_bounds__(kThreads, 1) void wgemm_atb_kernel(
     const short* __restrict__ a,  // [K, M]
     const short* __restrict__ b,  // [K, N]
     short* __restrict__ c,        // [M, N]
@@ -73,48 +96,50 @@ __global__ __launch_bounds__(kThreads, 2) void wgemm_atb_kernel(
   const int wm = wave >> 2;  // 0..1: wave's 128-row m strip
   const int wn = wave & 3;   // 0..3: wave's 64-col n strip
 
-  // XCD-aware tile swizzle (guide T1): the dispatcher places block b on
-  // XCD b%8, so by default neighboring tiles (which share operand
-  // panels) land on different L2s and the kernel runs into the HBM
-  // roofline (~7.2 TB/s effective measured without the swizzle).  The
-  // remap gives each XCD a contiguous M-major run of tiles: its ~32
-  // co-resident blocks then share one X panel (and neighboring dY
-  // panels) in its private L2.
-  int bx = blockIdx.x, by = blockIdx.y;
-  {
-    const int nwg = gridDim.x * gridDim.y;
-    if ((nwg & 7) == 0) {
-      const int swz = xcd_swizzle_m_major(
-          (int)(blockIdx.x + blockIdx.y * gridDim.x), nwg);
-      bx = swz % gridDim.x;
-      by = swz / gridDim.x;
-    }
-  }
+  // XCD-aware 2D tile clustering (mfma_tiles.h).  The operand panels
+  // of a 10B shape are re-fetched 20-60x across the grid (~40 GB per
+  // call, above HBM peak at the kernel's speed), so the kernel lives on
+  // L2 reuse; the clustered rectangle gives it on BOTH operands where
+  // the earlier M-major run reused one.
+  int bx, by;
+  xcd_cluster_tile(bx, by);
   const long m0 = (long)bx * kBM;
   const long n0 = (long)by * kBN;
 
-  // staging coordinates: thread t covers rows (t>>5) + i*16 at the
-  // constant column (t&31)*8 — pure expressions, no register arrays
-  constexpr int kVecs = kBK * (kBM / 8) / kThreads;  // 4
-  const int s_kr0 = tid >> 5;
-  const int s_c8 = (tid & 31) * 8;
-  bf16x8 a_st[kVecs], b_st[kVecs];
-  auto issue_loads = [&](long k_base) {
+  // DirectToLds staging: one global_load_lds(16 B) call deposits the
+  // wave's 64 lanes contiguously = k-rows R, R+1 of a tile, so lane l
+  // fills 16-B granule l&31 of row R + (l>>5) and fetches the source
+  // granule whose 32-byte chunk is XORed with chunk_xor(row).  4 calls
+  // per wave and operand cover the 64 rows.  No staging registers, no
+  // LDS write pass; synced by vmcnt + barrier.
+  constexpr int kCalls = kBK / 2 / (kThreads / 64);  // 4
+  auto issue_dtl = [&](int buf, long k_base) {
+    const int rsub = lane >> 5;
+    const int gl = lane & 31;
 #pragma unroll
-    for (int i = 0; i < kVecs; ++i) {
-      const long krow = k_base + s_kr0 + i * 16;
-      a_st[i] = *reinterpret_cast<const bf16x8*>(&a[krow * M + m0 + s_c8]);
-      b_st[i] = *reinterpret_cast<const bf16x8*>(&b[krow * N + n0 + s_c8]);
+    for (int i = 0; i < kCalls; ++i) {
+      const int R = (wave * kCalls + i) * 2;
+      const int k = R + rsub;
+      const int g = (((gl >> 1) ^ chunk_xor(k)) << 1) | (gl & 1);
+      glds16(&a[(k_base + k) * M + m0 + g * 8], &sm.a_tile[buf][R][0]);
+      glds16(&b[(k_base + k) * N + n0 + g * 8], &sm.b_tile[buf][R][0]);
     }
   };
-  auto write_tiles = [&](int buf) {
+
+  // fragment-read addresses: lane (seg, col) reads k-row
+  // kc*32 + seg*8 + 4h + (col>>2), 8 bytes at (col&3)*8 of the 32-byte
+  // chunk of its 16-column fragment; that row's chunk XOR is the lane
+  // constant xr, and (kc, h) move the address by a compile-time offset
+  const int xr = (col >> 2) | ((seg & 1) << 2);
+  const unsigned lane_off =
+      (unsigned)((seg * 8 + (col >> 2)) * kRowBytes + (col & 3) * 8);
+  unsigned a_off[8], b_off[4];
 #pragma unroll
-    for (int i = 0; i < kVecs; ++i) {
-      const int kr = s_kr0 + i * 16;
-      *reinterpret_cast<bf16x8*>(&sm.a_tile[buf][kr][s_c8]) = a_st[i];
-      *reinterpret_cast<bf16x8*>(&sm.b_tile[buf][kr][s_c8]) = b_st[i];
-    }
-  };
+  for (int mi = 0; mi < 8; ++mi)
+    a_off[mi] = lane_off + ((unsigned)((wm * 8 + mi) ^ xr) << 5);
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni)
+    b_off[ni] = lane_off + ((unsigned)((wn * 4 + ni) ^ xr) << 5);
 
   f32x4 acc[8][4];
 #pragma unroll
@@ -127,54 +152,47 @@ __global__ __launch_bounds__(kThreads, 2) void wgemm_atb_kernel(
   for (int mi = 0; mi < (WITH_BIAS ? 8 : 1); ++mi) bias_acc[mi] = 0.f;
 
   const int n_ksteps = K / kBK;
-  issue_loads(0);
-  write_tiles(0);
+  issue_dtl(0, 0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   for (int ks = 0; ks < n_ksteps; ++ks) {
     const int buf = ks & 1;
     const unsigned a_base = a_base0 + (unsigned)buf * kABufBytes;
     const unsigned b_base = b_base0 + (unsigned)buf * kBBufBytes;
+    // next K-step's tiles go to the OTHER buffer, whose last fragment
+    // reads retired (the mi = 7 lgkmcnt(0)) before the previous barrier
+    if (ks + 1 < n_ksteps) issue_dtl(buf ^ 1, (long)(ks + 1) * kBK);
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc) {
-      // next K-step's loads issue at the start of the SECOND chunk:
-      // their latency hides under its MFMAs and the staging registers
-      // stay live for only half the loop (register budget)
-      if (kc == 1 && ks + 1 < n_ksteps) issue_loads((long)(ks + 1) * kBK);
+      // one fragment = two transpose reads (the lane's k-row and the
+      // one 4 below) of chunk kc, at compile-time offsets from addr
+      auto rd = [&](unsigned addr, u32x2 (&f)[2]) {
+        if (kc == 0) {
+          f[0] = tr16_read_at<0>(addr);
+          f[1] = tr16_read_at<4 * kRowBytes>(addr);
+        } else {
+          f[0] = tr16_read_at<32 * kRowBytes>(addr);
+          f[1] = tr16_read_at<36 * kRowBytes>(addr);
+        }
+      };
       // B fragments for this 32-k chunk (8 tr reads, reused across mi)
       u32x2 bf[4][2];
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          bf[ni][h] = tr_read(b_base, col, kc * 32 + seg * 8 + 4 * h,
-                              wn * 64 + ni * 16, kSB);
-        }
-      }
+      for (int ni = 0; ni < 4; ++ni) rd(b_base + b_off[ni], bf[ni]);
       // A fragments stream through a 2-deep ring: af[mi+1] is issued
       // before the MFMAs of af[mi], with counted lgkmcnt waits.  The
       // waits carry the about-to-be-consumed fragments as "+v" operands
       // so the MFMAs cannot be scheduled above them (guide rule 18)
-      // without fencing the whole scheduler.  (A 4-slot ring with half
-      // the waits was tried: +8 live registers -> 44 VGPR spills, 2.3x
-      // slower.)
+      // without fencing the whole scheduler.  (All 24 reads up front
+      // under one wait, fgemm's v7 rung, measured 2% SLOWER here: the
+      // ring starts the MFMAs after 10 reads instead of 24.)
       u32x2 af[2][2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        af[0][h] = tr_read(a_base, col, kc * 32 + seg * 8 + 4 * h,
-                           wm * 128 + 0 * 16, kSA);
-      }
+      rd(a_base + a_off[0], af[0]);
 #pragma unroll
       for (int mi = 0; mi < 8; ++mi) {
         const int cur = mi & 1;
-        if (mi < 7) {
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            af[cur ^ 1][h] =
-                tr_read(a_base, col, kc * 32 + seg * 8 + 4 * h,
-                        wm * 128 + (mi + 1) * 16, kSA);
-          }
-        }
+        if (mi < 7) rd(a_base + a_off[mi + 1], af[cur ^ 1]);
         if (mi == 0) {
           // first wait also guards the B fragments (issued earlier,
           // retired in order before af[0]), which lds_wait's
@@ -214,10 +232,9 @@ __global__ __launch_bounds__(kThreads, 2) void wgemm_atb_kernel(
       }
     }
 
-    // single barrier per K-step: writes go to the OTHER buffer, so the
-    // only ordering needed is "this step's writes visible before the
-    // next step's reads"
-    if (ks + 1 < n_ksteps) write_tiles(buf ^ 1);
+    // single barrier per K-step: the next step's tiles (in flight
+    // since the top of this step) have landed and are visible
+    if (ks + 1 < n_ksteps) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
 

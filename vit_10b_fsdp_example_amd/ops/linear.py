@@ -1,57 +1,56 @@
 """Linear layer with a native weight-gradient kernel.
 
 Forward and the input-gradient GEMM go through hipBLASLt (the sanctioned
-library path for plain GEMMs); the weight gradient dW = dY^T X can route
+library path for plain GEMMs); the weight gradient dW = dY^T X routes
 through csrc/wgemm.hip (gfx950 ds_read_b64_tr_b16 hardware transpose
-reads, fused dbias column sums).
+reads on direct-to-LDS staged tiles) for the shapes where that kernel
+beats the library INSIDE the training step.
 
-Measured ISOLATED (benchmarks/bench_wgemm.py, K=32768):
-    shape (M=out, N=in)             ours    hipBLASLt
-    qkv   15360 x 5120               931        660  TF/s
-    proj   5120 x 5120               884        825
-    fc1   20480 x 5120               898       1076
-    fc2    5120 x 20480              918       1080
+Where the kernel stands (MI355X, K = 32768; receipts and the rung-by-rung
+table in profiles/PROFILES.md "wgemm NT ladder"):
 
-Measurement history (all on MI355X, receipts in profiles/PROFILES.md):
-  * first in-step number ~520 TF/s was caused by the FUSED dbias column
-    sums (per-fragment unpack+accumulate VALU, 945 -> 535 TF on the qkv
-    shape); dbias is now a separate memory-bound reduction;
-  * a cold-cache bench (4 rotating operand sets past the 256 MB L3)
-    confirmed the GEMM core itself beats hipBLASLt isolated;
-  * but a within-box end-to-end A/B still reads 54.3 vs 58.0 img/s with
-    the custom autograd Function active;
-  * per-layer isolation (benchmarks/bench_linear_bwd.py) shows stock,
-    Function-with-library-wgrad, and Function-with-native-wgrad all
-    EQUAL (qkv 12.9/12.6/12.9 ms fwd+bwd) — i.e. (a) torch's fused
-    linear backward already picks a dW kernel as fast as ours (the
-    standalone torch.matmul(a.t(), b) used as the bench baseline is the
-    SLOW formulation, not what training actually runs), and (b) the
-    end-to-end Function cost is an interaction with the grad-checkpoint
-    context, not a per-layer kernel effect;
-  * ROOT-CAUSED via benchmarks/ktrace_diff.py on the ON/OFF traces
-    (profiles/PROFILES.md "ktrace diff") + a CPU dispatch-count repro
-    (tests/test_checkpoint_earlystop.py): torch's codegen'd addmm packs
-    its input SavedVariables BEFORE dispatching the kernel, so
-    checkpoint(use_reentrant=False) early-stops the recompute before
-    the region's LAST GEMM (fc2 forward is never recomputed).  A custom
-    autograd.Function packs only after forward returns, so wrapping the
-    linears in one forces that GEMM back into every block recompute:
-    +128 forward GEMMs (+657 ms) per 4 profiled steps, ~164 ms/step —
-    which is the previously "unexplained" part of the A/B gap.  The
-    rest of the gap was the since-removed bias-fused wgemm variant.
-The corrected integration is VITFSDP_NATIVE_WGRAD=2 (NativeWgradMode
-below): dispatcher-level interception that keeps the stock addmm node.
-Measured on MI355X (ViT-Large bs=128, within-box where noted):
-  * mode 2 ungated: 1040 -> 702 img/s — the kernel has no split-K, so
-    ViT-Large dW grids (16-64 workgroups) cannot fill 256 CUs;
-  * mode 2 with the _MIN_TILES>=256 gate (nothing routed at Large):
-    117.4 ms/step vs 123.1 baseline (different boxes, within the ±5%
-    box variance) — the TorchDispatchMode python overhead itself is
-    NOT measurable: backward is GPU-bound and dispatch overlaps with
-    queued kernels.
-Both modes stay OPT-IN pending a ViT-10B within-box A/B (qkv/proj pass
-the gate there at 1200/400 workgroups); per-layer parity says expect
-neutral-to-small effect (ROADMAP item 4).
+    shape (M=out, N=in)     isolated, cold cache    in the ViT-10B step
+                            first    now            now    library
+    qkv   15360 x 5120      5.36     4.48 ms        4.64   5.09 ms   routed
+    proj   5120 x 5120      1.97     1.64           1.78   1.96      routed
+    fc1   20480 x 5120      7.66     6.43           6.41   6.29      library
+    fc2    5120 x 20480     7.46     6.56           6.45   6.24      library
+
+("first" is the register-staged first version of the kernel; all
+columns from one machine, the library in-step times from a trace of
+the step with the route off.)  The default route,
+VITFSDP_NATIVE_WGRAD=2, is the dispatcher-level interception below
+(NativeWgradMode, or the native_wgrad branch of TunedGemmMode); the
+shape gate _wgrad_mm_shapes_ok keeps fc1/fc2 on the library.
+VITFSDP_NATIVE_WGRAD=0 switches the route off.
+
+How the integration got here (all measured on MI355X):
+  * the dbias column sums are NOT fused into the GEMM: the per-fragment
+    unpack+accumulate VALU work cost 945 -> 535 TF/s on the qkv shape;
+    dbias stays a separate memory-bound reduction (the WITH_BIAS kernel
+    instantiation remains for the benchmark and its test);
+  * kernel timings use a cold-cache rotation (4 operand sets past the
+    256 MB L3): a single reused set flattered the kernel ~1.8x;
+  * wrapping the linears in a custom autograd.Function (mode "1") lost
+    ~164 ms/step: torch's codegen'd addmm packs its input SavedVariables
+    BEFORE dispatching the kernel, so checkpoint(use_reentrant=False)
+    early-stops the recompute before the region's LAST GEMM (fc2 forward
+    is never recomputed); a Function packs only after forward returns
+    and forces that GEMM back into every block recompute (+128 forward
+    GEMMs per 4 profiled steps; benchmarks/ktrace_diff.py on the ON/OFF
+    traces, CPU repro in tests/test_checkpoint_earlystop.py).  Mode "2"
+    keeps the stock addmm node and swaps only the kernel at dispatch
+    time, so the early-stop survives; the routed traces show no extra
+    forward GEMMs;
+  * the kernel has no split-K: ungated at ViT-Large (16-64 workgroup dW
+    grids) mode 2 ran 1040 -> 702 img/s, hence the _MIN_TILES >= 256
+    gate.  The TorchDispatchMode python overhead itself is not
+    measurable: backward is GPU-bound and dispatch overlaps with queued
+    kernels;
+  * with the first version of the kernel the route was neutral at 10B
+    (64.5 vs 65.0 img/s) and stayed opt-in; the ladder pass (clustered
+    2-D tile mapping, direct-to-LDS staging) made qkv and proj win
+    in-step by ~9%, which is what flipped the default.
 """
 
 import contextlib
@@ -69,8 +68,9 @@ from ..tuning import lt_algo_table
 # "1": custom autograd.Function (kept for A/B history; defeats checkpoint
 #      early-stop, see tests/test_checkpoint_earlystop.py)
 # "2": dispatcher interception below autograd (NativeWgradMode) — the
-#      stock addmm node stays, early-stop is preserved
-_WGRAD_MODE = os.environ.get("VITFSDP_NATIVE_WGRAD", "0")
+#      stock addmm node stays, early-stop is preserved.  The default.
+# "0": every dW GEMM stays on the library
+_WGRAD_MODE = os.environ.get("VITFSDP_NATIVE_WGRAD", "2")
 _NATIVE_WGRAD = _WGRAD_MODE == "1"
 _NATIVE_WGRAD_DISPATCH = _WGRAD_MODE == "2"
 
@@ -125,11 +125,13 @@ _MIN_TILES = int(os.environ.get("VITFSDP_WGRAD_MIN_TILES", "256"))
 
 def _wgrad_mm_shapes_ok(m, n, k):
     """Shape gate for the native wgrad kernel: the 256x256x64 tile must
-    divide evenly, the grid must be large enough to fill the chip
-    (_MIN_TILES), and the measured ViT-10B crossover keeps the very
-    wide/tall MLP shapes (fc1/fc2, 20480-wide) on hipBLASLt while qkv
-    and proj go native.  Symmetric bound because the dispatcher sees dW
-    in whichever orientation AddmmBackward chose."""
+    divide evenly (the same condition wgrad_gemm checks), the grid must
+    be large enough to fill the chip (_MIN_TILES), and only shapes that
+    beat the library in the ViT-10B step are routed: qkv (-0.45 ms per
+    call) and proj (-0.17 ms) go native, the 20480-wide MLP shapes stay
+    on hipBLASLt (fc1 +0.12 ms, fc2 +0.22 ms per call when routed).
+    Symmetric bound because the dispatcher sees dW in whichever
+    orientation AddmmBackward chose."""
     return (k % 64 == 0 and m % 256 == 0 and n % 256 == 0
             and m <= 16384 and n <= 16384
             and (m // 256) * (n // 256) >= _MIN_TILES)
