@@ -57,6 +57,12 @@ torch::Tensor fmha_bwd_qkv(torch::Tensor dout, torch::Tensor qkv,
                            long seed);
 torch::Tensor fmha_rowdot(torch::Tensor dout, torch::Tensor o);
 std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x);
+torch::Tensor dropout_fwd(torch::Tensor x, double p, long seed);
+torch::Tensor dropout_add_fwd(torch::Tensor x, torch::Tensor res, double p,
+                              long seed);
+torch::Tensor gelu_dropout_fwd(torch::Tensor x, double p, long seed);
+torch::Tensor gelu_dropout_bwd(torch::Tensor dy, torch::Tensor x, double p,
+                               long seed);
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma32_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor tr16_probe(long mode);
@@ -128,6 +134,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(dx, colsum): exact-erf GELU backward and the bf16 column sums "
         "of dx over all rows (fc1 bias gradient) in one pass",
         py::arg("dy"), py::arg("x"));
+  m.def("dropout_fwd", &dropout_fwd,
+        "hidden dropout with the in-kernel (seed, row, col) hash mask: "
+        "keep ? x / (1 - p) : 0; the same call on dy is its backward",
+        py::arg("x"), py::arg("p"), py::arg("seed"));
+  m.def("dropout_add_fwd", &dropout_add_fwd,
+        "x + dropout(res) in one pass (residual add with the branch's "
+        "dropout folded in), rounded once",
+        py::arg("x"), py::arg("res"), py::arg("p"), py::arg("seed"));
+  m.def("gelu_dropout_fwd", &gelu_dropout_fwd,
+        "dropout(gelu(x)) in one pass, exact-erf GELU, rounded once",
+        py::arg("x"), py::arg("p"), py::arg("seed"));
+  m.def("gelu_dropout_bwd", &gelu_dropout_bwd,
+        "backward of gelu_dropout_fwd from dy and the pre-activation x; "
+        "regenerates the mask from the seed",
+        py::arg("dy"), py::arg("x"), py::arg("p"), py::arg("seed"));
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("mfma32_probe", &mfma32_probe, "32x32x16 bf16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 semantics probe");

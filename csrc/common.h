@@ -34,6 +34,23 @@ __device__ __forceinline__ unsigned short f32_to_bf16(float f) {
   return cv.u;
 }
 
+// Dropout mask: stateless integer hash of (seed, row, column), so a
+// forward and its backward kernels regenerate the identical mask with no
+// stored bits.  keep iff hash >= threshold (threshold = p * 2^32);
+// integer-exact and reproduced bit-for-bit by the python reference
+// ops.attention.dropout_mask_reference.  Rows are the global q row
+// (incl. bh) in fmha.hip and the flattened row in dropout.hip.
+__device__ __forceinline__ unsigned dropout_hash(unsigned seed, unsigned qg,
+                                                 unsigned kg) {
+  unsigned x = seed ^ (qg * 0x9E3779B9u) ^ (kg * 0x85EBCA6Bu);
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 15;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+
 // full-wave sum: every lane ends with the 64-lane total
 __device__ __forceinline__ float wave_all_sum(float v) {
 #pragma unroll

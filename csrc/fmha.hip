@@ -104,21 +104,9 @@ struct QkvStrides {
   long ob, oh, ot;  // o (and dO) strides
 };
 
-// Attention-dropout mask: stateless integer hash of (seed, global q row
-// incl. bh, k column) so forward and both backward kernels regenerate
-// the identical mask with no stored bits.  keep iff hash >= threshold
-// (threshold = p * 2^32); integer-exact and reproduced bit-for-bit by
-// the python reference in tests/test_gpu_kernels.py.
-__device__ __forceinline__ unsigned dropout_hash(unsigned seed, unsigned qg,
-                                                 unsigned kg) {
-  unsigned x = seed ^ (qg * 0x9E3779B9u) ^ (kg * 0x85EBCA6Bu);
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
+// Attention-dropout mask: dropout_hash (common.h) of (seed, global q row
+// incl. bh, k column), so forward and both backward kernels regenerate
+// the identical mask with no stored bits.
 
 template <int D, bool DROP = false>
 // min 3 waves/SIMD: the double-buffered staging otherwise lands at

@@ -18,20 +18,11 @@
 #endif
 
 #include "common.h"
+#include "gelu_math.h"  // gelu_bwd_one, shared with dropout.hip
 
 namespace {
 
 constexpr int kBlock = 256;
-
-// d/dx gelu(x) * dy with gelu(x) = x * Phi(x): the formula (and fp32
-// evaluation) of torch's GeluBackward with approximate='none'
-__device__ __forceinline__ float gelu_bwd_one(float dy, float x) {
-  constexpr float kAlpha = 0.70710678118654752440f;     // 1/sqrt(2)
-  constexpr float kBeta = 0.39894228040143267794f;      // 1/sqrt(2*pi)
-  const float cdf = 0.5f * (1.f + erff(x * kAlpha));
-  const float pdf = expf(-0.5f * x * x) * kBeta;
-  return dy * (cdf + x * pdf);
-}
 
 __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_kernel(
     const ushort8_t* __restrict__ dy, const ushort8_t* __restrict__ x,

@@ -24,6 +24,7 @@ ext = CUDAExtension(
         "csrc/cross_entropy.hip",
         "csrc/fmha.hip",
         "csrc/gelu.hip",
+        "csrc/dropout.hip",
         "csrc/wgemm.hip",
         "csrc/fgemm.hip",
         "csrc/probes.hip",

@@ -26,12 +26,11 @@ recursive=True to init_vit_weights for the "intended" behavior.
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from .. import dist as xdist
 from ..ops import (  # noqa: F401
-    LayerNorm, NativeLinear, attention_qkv, cross_entropy,
-    fused_add_layer_norm,
+    HiddenDropout, LayerNorm, NativeLinear, attention_qkv, cross_entropy,
+    dropout_add, fused_add_layer_norm, gelu_dropout, hidden_dropout,
 )
 
 
@@ -102,7 +101,7 @@ class Attention(nn.Module):
         self.qkv = NativeLinear(dim, dim * 3, bias=qkv_bias)
         self.attn_drop_p = attn_drop
         self.proj = NativeLinear(dim, dim)
-        self.proj_drop = nn.Dropout(proj_drop)
+        self.proj_drop = HiddenDropout(proj_drop)
 
     def forward(self, x):
         B, T, E = x.shape
@@ -121,13 +120,18 @@ class Attention(nn.Module):
 
 
 class Mlp(nn.Module):
-    """fc1 -> GELU -> dropout -> fc2 -> dropout (timm Mlp)."""
+    """fc1 -> GELU -> dropout -> fc2 -> dropout (timm Mlp).
+
+    forward returns fc2's output BEFORE its dropout, together with the
+    dropout probability: the block applies that dropout itself, fused
+    into the residual add (ops.dropout_add) or, with the deferred
+    residual, as ops.hidden_dropout on the branch."""
 
     def __init__(self, dim, hidden_dim, drop=0.0):
         super().__init__()
         self.fc1 = NativeLinear(dim, hidden_dim)
         self.fc2 = NativeLinear(hidden_dim, dim)
-        self.drop = nn.Dropout(drop)
+        self.drop = HiddenDropout(drop)
         # register the MLP dims so the GEMM dispatch router can fuse the
         # GELU into the fc1/fc2 hipBLASLt epilogues (VITFSDP_FUSED_GELU)
         from ..ops.linear import configure_gelu_fusion
@@ -135,8 +139,9 @@ class Mlp(nn.Module):
         configure_gelu_fusion(dim, hidden_dim)
 
     def forward(self, x):
-        x = self.drop(F.gelu(self.fc1(x)))
-        return self.drop(self.fc2(x))
+        p = self.drop.p
+        x = gelu_dropout(self.fc1(x), p, self.training)
+        return self.fc2(x), p
 
 
 class Block(nn.Module):
@@ -175,8 +180,9 @@ class Block(nn.Module):
         x, normed = fused_add_layer_norm(
             x, attn_out, self.norm2.weight, self.norm2.bias, self.norm2.eps
         )
-        x = x + self.mlp(normed)
-        return x
+        # MLP residual add with fc2's dropout folded in
+        mlp_out, p = self.mlp(normed)
+        return dropout_add(x, mlp_out, p, self.training)
 
     def _forward_deferred(self, x):
         if isinstance(x, (tuple, list)):
@@ -192,7 +198,8 @@ class Block(nn.Module):
         s1, y1 = fused_add_layer_norm(
             s0, attn_out, self.norm2.weight, self.norm2.bias, self.norm2.eps
         )
-        return self.mlp(y1), s1
+        mlp_out, p = self.mlp(y1)
+        return hidden_dropout(mlp_out, p, self.training), s1
 
 
 class FSDPViTModel(nn.Module):
@@ -228,7 +235,7 @@ class FSDPViTModel(nn.Module):
         num_patches = self.patch_embed.num_patches
         self.pos_embed = nn.Parameter(torch.zeros(1, num_patches, embed_dim))
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
-        self.pos_drop = nn.Dropout(pos_dropout)
+        self.pos_drop = HiddenDropout(pos_dropout)
 
         blocks = []
         for idx in range(num_blocks):

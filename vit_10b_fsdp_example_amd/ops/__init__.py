@@ -8,6 +8,11 @@ from .linear import (
     NativeLinear, NativeWgradMode, TunedGemmMode, gemm_dispatch_context,
     wgrad_backward_context,
 )
+from .dropout import (
+    HiddenDropout, dropout_add, dropout_add_reference, gelu_dropout,
+    gelu_dropout_reference, hidden_dropout, hidden_dropout_mask,
+    hidden_dropout_reference,
+)
 
 __all__ = [
     "ext",
@@ -29,4 +34,12 @@ __all__ = [
     "TunedGemmMode",
     "gemm_dispatch_context",
     "wgrad_backward_context",
+    "HiddenDropout",
+    "hidden_dropout",
+    "dropout_add",
+    "gelu_dropout",
+    "hidden_dropout_mask",
+    "hidden_dropout_reference",
+    "dropout_add_reference",
+    "gelu_dropout_reference",
 ]
