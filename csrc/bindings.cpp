@@ -57,6 +57,10 @@ torch::Tensor fmha_bwd_qkv(torch::Tensor dout, torch::Tensor qkv,
                            long seed);
 torch::Tensor fmha_rowdot(torch::Tensor dout, torch::Tensor o);
 std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x);
+std::vector<torch::Tensor> gelu_bwd_colsum_t(torch::Tensor dy,
+                                             torch::Tensor x);
+torch::Tensor transpose2d(torch::Tensor x);
+std::vector<torch::Tensor> transpose_colsum(torch::Tensor x);
 torch::Tensor dropout_fwd(torch::Tensor x, double p, long seed);
 torch::Tensor dropout_add_fwd(torch::Tensor x, torch::Tensor res, double p,
                               long seed);
@@ -134,6 +138,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(dx, colsum): exact-erf GELU backward and the bf16 column sums "
         "of dx over all rows (fc1 bias gradient) in one pass",
         py::arg("dy"), py::arg("x"));
+  m.def("gelu_bwd_colsum_t", &gelu_bwd_colsum_t,
+        "(dx, colsum, dx^T): gelu_bwd_colsum with dx^T [hid, rows] as a "
+        "third output; dx and colsum are bit-identical to gelu_bwd_colsum's",
+        py::arg("dy"), py::arg("x"));
+  m.def("transpose2d", &transpose2d,
+        "bf16 [R, C] contiguous -> [C, R] contiguous (C % 8 == 0)",
+        py::arg("x"));
+  m.def("transpose_colsum", &transpose_colsum,
+        "(x^T, colsum): transpose2d plus the bf16 column sums of x over "
+        "all rows (a linear's bias gradient) from the same read; fp32 "
+        "accumulation in a fixed order",
+        py::arg("x"));
   m.def("dropout_fwd", &dropout_fwd,
         "hidden dropout with the in-kernel (seed, row, col) hash mask: "
         "keep ? x / (1 - p) : 0; the same call on dy is its backward",

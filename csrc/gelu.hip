@@ -17,6 +17,7 @@
 #include <torch/extension.h>
 #endif
 
+#include "colsum_final.h"  // partials -> bf16 sums, shared with transpose.hip
 #include "common.h"
 #include "gelu_math.h"  // gelu_bwd_one, shared with dropout.hip
 
@@ -53,40 +54,124 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_kernel(
   p[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
 }
 
-// [n_chunks, hid] fp32 partials -> bf16 column sums.  A block owns 32
-// columns and splits the chunks over 8 slices that meet in LDS, so
-// hid = 20480 gives 640 blocks reading 128-byte row segments.
-constexpr int kFinalCols = 32;
-constexpr int kFinalSlices = kBlock / kFinalCols;
+// The same, and dx^T [hid, rows] as a third output for the TN weight
+// gradient of fc1 (ops/linear.py), so that dx is not read back for a
+// transpose.  dx, the partials and hence the column sums are bit-identical
+// to gelu_bwd_colsum_kernel's: the chunks are the same, and every
+// column's fp32 sum still takes its rows one by one in row order.
+//
+// The thread-per-vector-column walk above cannot write dx^T in useful
+// pieces (16 bytes per thread per row), so a block moves 64-row x
+// 256-column tiles, aligned to multiples of 64 rows, through 32 KB of LDS
+// in three phases: (A) each thread computes eight 16-byte vectors, writes
+// them to dx and to the tile; (B) thread t walks column t down the tile's
+// rows of this chunk, adding to its running sum; (C) as in transpose.hip,
+// 8 lanes assemble one 128-byte segment of a dx^T row from 16-bit column
+// reads.  The tile row holds 32 16-byte slots at slot ^ (row / 8 % 8), so
+// the 8 lanes of (C) land in 8 different 4-bank groups.  A chunk is not a
+// multiple of 8 rows in general (161 at 32768 x 20480): the 8-row groups
+// that straddle a chunk boundary, and every group when rows % 8 != 0, are
+// stored by element.
+constexpr int kTRows = 64;
+constexpr int kTCols = 256;
+constexpr int kTSlots = kTCols / 8;
 
-__global__ __launch_bounds__(kBlock) void gelu_colsum_final_kernel(
-    const float* __restrict__ part, unsigned short* __restrict__ out, int hid,
-    int n_chunks) {
-  __shared__ float s_s[kFinalSlices][kFinalCols];
-  const int c = threadIdx.x % kFinalCols;
-  const int slice = threadIdx.x / kFinalCols;
-  const int col = blockIdx.x * kFinalCols + c;
-  float s = 0.f;
-  if (col < hid) {
-#pragma unroll 4
-    for (int ch = slice; ch < n_chunks; ch += kFinalSlices)
-      s += part[(long)ch * hid + col];
-  }
-  s_s[slice][c] = s;
-  __syncthreads();
-  if (slice == 0 && col < hid) {
+__global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
+    const unsigned short* __restrict__ dy, const unsigned short* __restrict__ x,
+    unsigned short* __restrict__ dx, unsigned short* __restrict__ dxt,
+    float* __restrict__ part, long hid, long n_rows, int rows_per_chunk) {
+  __shared__ ushort8_t tile[kTRows * kTSlots];
+  const unsigned short* tile_s = reinterpret_cast<const unsigned short*>(tile);
+  const int t = threadIdx.x;
+  const long c0 = (long)blockIdx.x * kTCols;
+  const long row_begin = (long)blockIdx.y * rows_per_chunk;
+  const long row_end = min(row_begin + rows_per_chunk, n_rows);
+  const bool vec_store = (n_rows & 7) == 0;  // dx^T rows 16-byte aligned
+  const int a_slot = t & 31, a_row = t >> 5;  // (A): rows a_row + 8k
+  const bool a_col_ok = c0 + a_slot * 8 < hid;
+  const int c_hi = t >> 3, c_lo = t & 7;  // (C): column c_hi + 32k, rows 8 c_lo..
+  float acc = 0.f;
+
+  for (long tr0 = row_begin & ~(long)(kTRows - 1); tr0 < row_end;
+       tr0 += kTRows) {
 #pragma unroll
-    for (int k = 1; k < kFinalSlices; ++k) s += s_s[k][c];
-    out[col] = f32_to_bf16(s);
+    for (int k = 0; k < 8; ++k) {
+      const int r = a_row + 8 * k;
+      const long gr = tr0 + r;
+      if (a_col_ok && gr >= row_begin && gr < row_end) {
+        const long i = gr * hid + c0 + a_slot * 8;
+        const ushort8_t dv = *reinterpret_cast<const ushort8_t*>(dy + i);
+        const ushort8_t xv = *reinterpret_cast<const ushort8_t*>(x + i);
+        ushort8_t out;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          out[j] = f32_to_bf16(
+              gelu_bwd_one(bf16_to_f32(dv[j]), bf16_to_f32(xv[j])));
+        *reinterpret_cast<ushort8_t*>(dx + i) = out;
+        tile[r * kTSlots + (a_slot ^ ((r >> 3) & 7))] = out;
+      }
+    }
+    __syncthreads();
+    // rows and columns outside the chunk or the tensor were not written
+    // to the tile; (B) and (C) read none of them
+    if (c0 + t < hid) {
+      const int rb = (int)max(row_begin - tr0, 0L);
+      const int re = (int)min(row_end - tr0, (long)kTRows);
+      const int slot = t >> 3, e = t & 7;
+      for (int r = rb; r < re; ++r)
+        acc += bf16_to_f32(
+            tile_s[r * kTCols + ((slot ^ ((r >> 3) & 7)) << 3) + e]);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int c = c_hi + 32 * k;
+      const long gr = tr0 + c_lo * 8;  // first row of this 8-row group
+      if (c0 + c < hid && gr < row_end && gr + 8 > row_begin) {
+        const unsigned short* src =
+            tile_s + (c_lo * 8) * kTCols + (((c >> 3) ^ c_lo) << 3) + (c & 7);
+        unsigned short* dst = dxt + (c0 + c) * n_rows + gr;
+        if (vec_store && gr >= row_begin && gr + 8 <= row_end) {
+          ushort8_t o;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o[j] = src[j * kTCols];
+          *reinterpret_cast<ushort8_t*>(dst) = o;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (gr + j >= row_begin && gr + j < row_end) dst[j] = src[j * kTCols];
+        }
+      }
+    }
+    __syncthreads();
   }
+  if (c0 + t < hid) part[(long)blockIdx.y * hid + c0 + t] = acc;
 }
 
 }  // namespace
 
 #ifndef VITFSDP_KERNELS_ONLY
+namespace {
+
 // dy, x: bf16 [rows, hid] contiguous (any leading dims), hid % 8 == 0.
-// Returns (dx like dy, colsum bf16 [hid]).
+// Returns (dx like dy, colsum bf16 [hid]) and, with_t, dx^T [hid, rows].
+std::vector<torch::Tensor> gelu_bwd_colsum_run(torch::Tensor dy,
+                                               torch::Tensor x, bool with_t);
+
+}  // namespace
+
 std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x) {
+  return gelu_bwd_colsum_run(dy, x, false);
+}
+
+std::vector<torch::Tensor> gelu_bwd_colsum_t(torch::Tensor dy,
+                                             torch::Tensor x) {
+  return gelu_bwd_colsum_run(dy, x, true);
+}
+
+namespace {
+
+std::vector<torch::Tensor> gelu_bwd_colsum_run(torch::Tensor dy,
+                                               torch::Tensor x, bool with_t) {
   TORCH_CHECK(dy.is_cuda() && x.is_cuda() && dy.is_contiguous() &&
                   x.is_contiguous(),
               "gelu_bwd_colsum: contiguous GPU tensors");
@@ -102,9 +187,12 @@ std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x) {
   const long n = dy.numel() / hid;
   auto dx = torch::empty_like(dy);
   auto colsum = torch::empty({hid}, dy.options());
+  torch::Tensor dxt;
+  if (with_t) dxt = torch::empty({hid, n}, dy.options());
   if (n == 0) {
     colsum.zero_();
-    return {dx, colsum};
+    return with_t ? std::vector<torch::Tensor>{dx, colsum, dxt}
+                  : std::vector<torch::Tensor>{dx, colsum};
   }
   const int nvec = (int)(hid / 8);
   // row chunking: ~2048 blocks in all (256 CUs x 8), at least 16 rows
@@ -117,17 +205,32 @@ std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x) {
   auto part = torch::empty({n_chunks, hid},
                            dy.options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(gelu_bwd_colsum_kernel, dim3(grid_x, (unsigned)n_chunks),
-                     dim3(kBlock), 0, stream, (const ushort8_t*)dy.data_ptr(),
-                     (const ushort8_t*)x.data_ptr(), (ushort8_t*)dx.data_ptr(),
-                     part.data_ptr<float>(), nvec, n, (int)rows_per_chunk);
+  if (with_t) {
+    // the same chunks, so the same partials; only the block shape differs
+    hipLaunchKernelGGL(
+        gelu_bwd_colsum_t_kernel,
+        dim3((unsigned)((hid + kTCols - 1) / kTCols), (unsigned)n_chunks),
+        dim3(kBlock), 0, stream, (const unsigned short*)dy.data_ptr(),
+        (const unsigned short*)x.data_ptr(), (unsigned short*)dx.data_ptr(),
+        (unsigned short*)dxt.data_ptr(), part.data_ptr<float>(), hid, n,
+        (int)rows_per_chunk);
+  } else {
+    hipLaunchKernelGGL(gelu_bwd_colsum_kernel,
+                       dim3(grid_x, (unsigned)n_chunks), dim3(kBlock), 0,
+                       stream, (const ushort8_t*)dy.data_ptr(),
+                       (const ushort8_t*)x.data_ptr(),
+                       (ushort8_t*)dx.data_ptr(), part.data_ptr<float>(), nvec,
+                       n, (int)rows_per_chunk);
+  }
   HIP_CHECK_LAST();
-  hipLaunchKernelGGL(gelu_colsum_final_kernel,
-                     dim3((unsigned)((hid + kFinalCols - 1) / kFinalCols)),
-                     dim3(kBlock), 0, stream, part.data_ptr<float>(),
+  hipLaunchKernelGGL(colsum_final_kernel, colsum_final_grid(hid),
+                     dim3(kColsumFinalBlock), 0, stream, part.data_ptr<float>(),
                      (unsigned short*)colsum.data_ptr(), (int)hid,
                      (int)n_chunks);
   HIP_CHECK_LAST();
+  if (with_t) return {dx, colsum, dxt};
   return {dx, colsum};
 }
+
+}  // namespace
 #endif  // VITFSDP_KERNELS_ONLY

@@ -13,12 +13,16 @@ table in profiles/PROFILES.md "wgemm NT ladder"):
                             first    now            now    library
     qkv   15360 x 5120      5.36     4.48 ms        4.64   5.09 ms   routed
     proj   5120 x 5120      1.97     1.64           1.78   1.96      routed
-    fc1   20480 x 5120      7.66     6.43           6.41   6.29      library
-    fc2    5120 x 20480     7.46     6.56           6.45   6.24      library
+    fc1   20480 x 5120      7.66     6.43           6.41   6.29      library TN
+    fc2    5120 x 20480     7.46     6.56           6.45   6.24      library TN
 
 ("first" is the register-staged first version of the kernel; all
 columns from one machine, the library in-step times from a trace of
-the step with the route off.)  The default route,
+the step with the route off.)  "library TN": fc1 and fc2 no longer run
+the library's NT kernel either; they run its TN kernel on operands
+transposed by csrc/transpose.hip (the "TN weight gradients" section
+below: 5.2-5.4 ms per call with both transposes and the bias sums,
+VITFSDP_TN_WGRAD).  The default route,
 VITFSDP_NATIVE_WGRAD=2, is the dispatcher-level interception below
 (NativeWgradMode, or the native_wgrad branch of TunedGemmMode); the
 shape gate _wgrad_mm_shapes_ok keeps fc1/fc2 on the library.
@@ -137,20 +141,132 @@ def _wgrad_mm_shapes_ok(m, n, k):
             and (m // 256) * (n // 256) >= _MIN_TILES)
 
 
-def _is_wgrad_mm(at, b):
-    """Match the weight-gradient GEMM AddmmBackward emits:
-    mm(saved_input.t(), grad_out) — first operand a transposed view of a
-    contiguous [K, M] base, second operand contiguous [K, N]."""
+def _wgrad_mm_dims(at, b):
+    """(m, n, k) if mm(at, b) has the layout of the weight-gradient GEMM
+    AddmmBackward emits — first operand a transposed view of a
+    contiguous [K, M] base, second operand contiguous [K, N] — else
+    None."""
     if at.dim() != 2 or b.dim() != 2 or at.shape[1] != b.shape[0]:
-        return False
+        return None
     m, k = at.shape
     if m < 2 or k < 2:
-        return False  # degenerate strides are ambiguous
+        return None  # degenerate strides are ambiguous
     if not (at.stride(0) == 1 and at.stride(1) == m):
-        return False
+        return None
     if not (b.stride(1) == 1 and b.stride(0) == b.shape[1]):
+        return None
+    return m, b.shape[1], k
+
+
+def _is_wgrad_mm(at, b):
+    """The weight-gradient GEMM, at a shape the native kernel takes."""
+    dims = _wgrad_mm_dims(at, b)
+    return dims is not None and _wgrad_mm_shapes_ok(*dims)
+
+
+# --------------------------------------------------------------------------
+# Weight gradients as library TN GEMMs on transposed operands
+# (csrc/transpose.hip).  In dW[out, in] = dY^T X both operands have the
+# token index as the slow dimension, the NT form, which the library runs
+# 30-40 % slower than its TN form at these sizes.  Transposing both
+# operands is memory traffic at ~5 TB/s against a compute-bound GEMM,
+# and the pass over dY also yields dY's column sums, the bias gradient,
+# so the separate reduction goes too.  AddmmBackward on this torch emits
+#     mm(dy, W) ; mm(dy.t(), x) -> [out, in] ; sum.dim_IntList(dy, [0], True)
+# and the route answers the second and third; either may come first.
+#
+# MI355X, K = 32768, ms per call, isolated with cold-cache rotation
+# (benchmarks/bench_tn_wgrad.py; profiles/PROFILES.md "TN wgrad"):
+#
+#     shape (out x in)     NT GEMM + sum       TN GEMM   transposes + TN
+#     fc1  20480 x 5120    6.29 + 0.24         4.68      5.23    routed
+#     fc2   5120 x 20480   6.30 + 0.07         4.80      5.41    routed
+#     qkv  15360 x 5120    4.53 + 0.18         4.02      4.48    wgemm.hip
+#     proj  5120 x 5120    1.61 + 0.07         1.81      2.12    wgemm.hip
+#
+# In the step fc1 and fc2 gain 1.17 and 1.03 ms per call (1927 -> 1864
+# ms/step); fc1's dy^T is a third output of the GELU backward
+# (_C.gelu_bwd_colsum_t, VITFSDP_TN_DGELU_T).  qkv gains 0.38 ms per call in the step trace, but isolated
+# on one machine it leads the wgemm.hip path by 1-3 % only, inside the spread
+# of the parent's own samples, so it stays on wgemm.hip.
+# VITFSDP_TN_WGRAD=0 turns the route off.
+# --------------------------------------------------------------------------
+
+# (out, in) of the dW shapes that won both isolated and in the step
+_TN_WGRAD_SHAPES = frozenset({(20480, 5120), (5120, 20480)})
+
+# The measurements are at K = 32768.  Transpose bytes and GEMM FLOPs both
+# scale with K, so their ratio holds at other batch sizes; the floor only
+# keeps the route away from GEMMs too short to be compute-bound.
+_TN_WGRAD_MIN_K = 4096
+
+# Experiments and tests: when >= 0, every dW with out * in >= this many
+# elements is routed whatever the table and the K floor say.
+_TN_MIN_ELEMS = int(os.environ.get("VITFSDP_TN_WGRAD_MIN_ELEMS", "-1"))
+
+
+def _tn_wgrad_on():
+    return os.environ.get("VITFSDP_TN_WGRAD", "1") != "0"
+
+
+def _tn_dgelu_t_on():
+    """fc1's dy^T as a third output of the GELU backward
+    (_C.gelu_bwd_colsum_t) instead of a transpose2d of its result."""
+    return os.environ.get("VITFSDP_TN_DGELU_T", "1") != "0"
+
+
+def _tn_wgrad_shapes_ok(m, n, k):
+    """Shape gate of the TN route for dW [m = out, n = in] over k rows.
+    Both transposes need a multiple of 8 columns."""
+    if m % 8 or n % 8:
         return False
-    return _wgrad_mm_shapes_ok(m, b.shape[1], k)
+    if _TN_MIN_ELEMS >= 0:
+        return m * n >= _TN_MIN_ELEMS
+    return (m, n) in _TN_WGRAD_SHAPES and k >= _TN_WGRAD_MIN_K
+
+
+def _tn_wgrad_out_ok(m, k):
+    """The gate as far as it can be told from dy [k, m] alone, for a
+    bias sum that arrives before its GEMM."""
+    if m % 8 or k < 2:
+        return False
+    if _TN_MIN_ELEMS >= 0:
+        return True
+    return k >= _TN_WGRAD_MIN_K and any(m == s[0] for s in _TN_WGRAD_SHAPES)
+
+
+def _same_buffer(t, ref):
+    """t is the tensor ref or a same-sized contiguous view of it whose
+    rows have ref's length (the identity test of the parked sums)."""
+    return (
+        t.dtype == ref.dtype
+        and t.device == ref.device
+        and t.untyped_storage().data_ptr() == ref.untyped_storage().data_ptr()
+        and t.storage_offset() == ref.storage_offset()
+        and t.numel() == ref.numel()
+        and t.dim() >= 2
+        and t.shape[-1] == ref.shape[-1]
+        and t.is_contiguous()
+    )
+
+
+def _row_sum_args(args, kwargs):
+    """(t, keepdim) if this sum.dim_IntList reduces every dim but the
+    last of a contiguous tensor with no dtype change, else None."""
+    if kwargs.get("dtype") is not None:
+        return None
+    t = args[0]
+    dims = args[1] if len(args) > 1 else None
+    keepdim = args[2] if len(args) > 2 else kwargs.get("keepdim", False)
+    if not (
+        isinstance(t, torch.Tensor)
+        and dims is not None
+        and t.dim() >= 2
+        and t.is_contiguous()
+        and sorted(d % t.dim() for d in dims) == list(range(t.dim() - 1))
+    ):
+        return None
+    return t, keepdim
 
 
 class NativeWgradMode(TorchDispatchMode):
@@ -301,13 +417,14 @@ class TunedGemmMode(TorchDispatchMode):
     NativeWgradMode, so the autograd graph keeps its stock addmm/mm
     nodes and non-reentrant checkpoint early-stop is preserved.
 
-    Also hosts the native-wgrad reroute when VITFSDP_NATIVE_WGRAD=2 and
-    the fused MLP GELU epilogues when configured, so one mode covers
-    the whole step (push around forward AND backward).
+    Also hosts the native-wgrad reroute when VITFSDP_NATIVE_WGRAD=2, the
+    TN weight-gradient route (which takes precedence at the shapes in
+    its gate) and the fused MLP GELU epilogues when configured, so one
+    mode covers the whole step (push around forward AND backward).
     """
 
     def __init__(self, table=None, native_wgrad=None, handler=None,
-                 dgelu_handler=None):
+                 dgelu_handler=None, tn_handler=None):
         super().__init__()
         self.table = lt_algo_table() if table is None else table
         self.native_wgrad = (
@@ -332,12 +449,33 @@ class TunedGemmMode(TorchDispatchMode):
         self.fused_dgelu = _dgelu_dbias_on() and (
             dgelu_handler is not None or self._handler is None
         )
-        self._dgelu_stash = None  # (dx, colsum): at most one entry
+        # (dx, colsum, dx^T or None): at most one entry
+        self._dgelu_stash = None
         self.dgelu_hits = 0
         self.dbias_hits = 0
+        # TN weight gradients (see module comment above).
+        # test seam: tn_handler(t, want_colsum) -> (t^T contiguous,
+        # column sums or None) replaces _C.transpose2d /
+        # _C.transpose_colsum; the GEMM goes through ``handler``
+        self._tn_handler = tn_handler
+        self.tn_wgrad = _tn_wgrad_on() and (
+            tn_handler is not None or self._handler is None
+        )
+        # (dy, colsum, dyT), at most one entry, holding dy so that its
+        # address cannot be recycled.  After the GEMM: colsum waits for
+        # the bias sum, dyT is None.  After a bias sum that came first:
+        # dyT waits for the GEMM, colsum is None.
+        self._tn_stash = None
+        self.tn_dgelu_t = self.tn_wgrad and _tn_dgelu_t_on()
+        # set by the first routed GEMM that found no dy^T parked: the
+        # sums follow their GEMMs here and none needs a pass of its own
+        self._tn_mm_first = False
+        self.tn_hits = 0
+        self.tn_dbias_hits = 0
 
     def __exit__(self, exc_type, exc_val, exc_tb):
         self._dgelu_stash = None
+        self._tn_stash = None
         return super().__exit__(exc_type, exc_val, exc_tb)
 
     def _tuned_index(self, a, b):
@@ -414,43 +552,114 @@ class TunedGemmMode(TorchDispatchMode):
         )
 
     def _fused_dgelu(self, dy, x):
+        hid = dy.shape[-1]
+        # fc1's weight gradient will want dx^T if it takes the TN route
+        want_t = self.tn_dgelu_t and _tn_wgrad_shapes_ok(
+            hid, _GELU_CFG["d"], dy.numel() // hid)
+        dxt = None
         if self._dgelu_handler is not None:
             dx, colsum = self._dgelu_handler(dy, x)
+            if want_t:
+                dxt = dx.reshape(-1, hid).t().contiguous()
+        elif want_t:
+            dx, colsum, dxt = ext().gelu_bwd_colsum_t(dy, x)
         else:
             # a missing kernel is an error here, not a fallback
             dx, colsum = ext().gelu_bwd_colsum(dy, x)
         self.dgelu_hits += 1
         # holding dx keeps its address from being recycled while the
         # entry lives; the next gelu_backward overwrites it
-        self._dgelu_stash = (dx, colsum)
+        self._dgelu_stash = (dx, colsum, dxt)
         return dx
 
     def _stashed_dbias(self, args, kwargs):
         """The parked column sums if this sum is dx.sum over every dim
         but the last, else None."""
-        if self._dgelu_stash is None or kwargs.get("dtype") is not None:
+        rs = _row_sum_args(args, kwargs)
+        if self._dgelu_stash is None or rs is None:
             return None
-        dx, colsum = self._dgelu_stash
-        t = args[0]
-        dims = args[1] if len(args) > 1 else None
-        keepdim = args[2] if len(args) > 2 else kwargs.get("keepdim", False)
-        if not (
-            isinstance(t, torch.Tensor)
-            and dims is not None
-            and t.dtype == dx.dtype
-            and t.device == dx.device
-            and t.untyped_storage().data_ptr()
-            == dx.untyped_storage().data_ptr()
-            and t.storage_offset() == dx.storage_offset()
-            and t.numel() == dx.numel()
-            and t.dim() >= 2
-            and t.shape[-1] == dx.shape[-1]
-            and t.is_contiguous()
-            and sorted(d % t.dim() for d in dims) == list(range(t.dim() - 1))
-        ):
+        dx, colsum = self._dgelu_stash[:2]
+        t, keepdim = rs
+        if not _same_buffer(t, dx):
             return None
         self._dgelu_stash = None
         self.dbias_hits += 1
+        if keepdim:
+            return colsum.view([1] * (t.dim() - 1) + [t.shape[-1]])
+        return colsum
+
+    # -- TN weight-gradient helpers ------------------------------------------
+
+    def _tn_transposed(self, t, want_colsum):
+        """(t^T contiguous, bf16 column sums of t or None)."""
+        if self._tn_handler is not None:
+            return self._tn_handler(t, want_colsum)
+        # a missing kernel is an error here, not a fallback
+        if want_colsum:
+            tt, colsum = ext().transpose_colsum(t)
+            return tt, colsum
+        return ext().transpose2d(t), None
+
+    def _is_tn_wgrad_mm(self, at, b):
+        dims = _wgrad_mm_dims(at, b)
+        if dims is None or not _tn_wgrad_shapes_ok(*dims):
+            return False
+        return self._handler is not None or b.dtype == torch.bfloat16
+
+    def _tn_wgrad(self, at, x):
+        """dW [out, in] contiguous = lt_gemm(dy^T, (x^T).t()).  The two
+        transposes live only until the GEMM is queued."""
+        dy = at.t()  # the contiguous [K, out] base
+        st, self._tn_stash = self._tn_stash, None
+        if st is not None and st[2] is not None and _same_buffer(dy, st[0]):
+            dyT = st[2]  # its bias sum came first and did the pass
+        else:
+            # on this torch the GEMM comes first: stop guessing at sums
+            self._tn_mm_first = True
+            if self._dgelu_stash is not None and _same_buffer(
+                    dy, self._dgelu_stash[0]):
+                # fc1: dy is the GELU backward's result, whose column
+                # sums that kernel has parked already, with dy^T if it
+                # was told to write it
+                dx, colsum, dyT = self._dgelu_stash
+                if dyT is None:
+                    dyT, _ = self._tn_transposed(dy, False)
+                else:
+                    self._dgelu_stash = (dx, colsum, None)
+            else:
+                dyT, colsum = self._tn_transposed(dy, True)
+                self._tn_stash = (dy, colsum, None)
+        xT, _ = self._tn_transposed(x, False)
+        b = xT.t()
+        idx = self._tuned_index(dyT, b)
+        self.tn_hits += 1
+        return self._route(dyT, b, -1 if idx is None else idx)
+
+    def _tn_dbias(self, args, kwargs):
+        """The column sums of dy for its bias gradient: the ones the
+        GEMM parked, or — when the sum comes before its GEMM — from the
+        pass done here, which parks dy^T for the GEMM.  Else None."""
+        rs = _row_sum_args(args, kwargs)
+        if rs is None:
+            return None
+        t, keepdim = rs
+        st = self._tn_stash
+        if st is not None and st[1] is not None and _same_buffer(t, st[0]):
+            colsum = st[1]
+            self._tn_stash = None
+        elif (
+            not self._tn_mm_first
+            and t.dim() == 2
+            and self._gpu_ok(t)
+            and _tn_wgrad_out_ok(t.shape[1], t.shape[0])
+        ):
+            # the GEMM's other operand is not known yet, so this goes by
+            # dy's shape alone; a GEMM outside the gate leaves dy^T unused
+            dyT, colsum = self._tn_transposed(t, True)
+            self._tn_stash = (t, None, dyT)
+        else:
+            return None
+        self.tn_dbias_hits += 1
         if keepdim:
             return colsum.view([1] * (t.dim() - 1) + [t.shape[-1]])
         return colsum
@@ -459,6 +668,8 @@ class TunedGemmMode(TorchDispatchMode):
         kwargs = kwargs or {}
         if func is torch.ops.aten.mm.default and self._gpu_ok(args[0]):
             a, b = args
+            if self.tn_wgrad and self._is_tn_wgrad_mm(a, b):
+                return self._tn_wgrad(a, b)
             if (
                 self.native_wgrad
                 and self._handler is None
@@ -501,11 +712,14 @@ class TunedGemmMode(TorchDispatchMode):
         elif self.fused_dgelu and func is torch.ops.aten.gelu_backward.default:
             if self._is_mlp_dgelu(args, kwargs):
                 return self._fused_dgelu(*args)
-        elif (
-            self._dgelu_stash is not None
-            and func is torch.ops.aten.sum.dim_IntList
+        elif func is torch.ops.aten.sum.dim_IntList and (
+            self._dgelu_stash is not None or self.tn_wgrad
         ):
-            out = self._stashed_dbias(args, kwargs)
+            out = None
+            if self._dgelu_stash is not None:
+                out = self._stashed_dbias(args, kwargs)
+            if out is None and self.tn_wgrad:
+                out = self._tn_dbias(args, kwargs)
             if out is not None:
                 return out
         return func(*args, **kwargs)
@@ -516,7 +730,10 @@ def gemm_dispatch_context():
     activates the dispatcher-level GEMM rerouting when the tuned
     algorithm table is present, fused MLP GELU or the fused
     dgelu + bias-gradient pass is configured, or VITFSDP_NATIVE_WGRAD=2;
-    otherwise a no-op."""
+    otherwise a no-op.  The TN weight-gradient route (VITFSDP_TN_WGRAD)
+    lives in TunedGemmMode and is active whenever that mode is; it does
+    not bring the mode up on its own: with the tuned table disabled and
+    the fused dgelu off, the step is the plain NativeWgradMode one."""
     if lt_algo_table() or _gelu_fusion_on() or _dgelu_dbias_on():
         return TunedGemmMode()
     if _NATIVE_WGRAD_DISPATCH:
