@@ -85,6 +85,7 @@ std::vector<torch::Tensor> lt_gemm_dgelu_bgrad(torch::Tensor dy,
                                                torch::Tensor w,
                                                torch::Tensor aux,
                                                long algo_index);
+torch::Tensor dgrad_tn(torch::Tensor dy, torch::Tensor w, long algo_index);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native CDNA4 kernels for the FSDP ViT framework";
@@ -195,4 +196,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "GEMM (DGELU_BGRAD epilogue)",
         py::arg("dy"), py::arg("w"), py::arg("aux"),
         py::arg("algo_index") = -1);
+  m.def("dgrad_tn", &dgrad_tn,
+        "dx [tok, in] = dy [tok, out] @ w [out, in] as the library's TN "
+        "GEMM on w^T, which csrc/transpose.hip writes into a scratch "
+        "buffer on every call; row-contiguous bf16 operands, in and out "
+        "multiples of 8, w 16-byte aligned",
+        py::arg("dy"), py::arg("w"), py::arg("algo_index") = -1);
 }

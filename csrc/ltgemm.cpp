@@ -8,6 +8,7 @@
 //   d        = _C.lt_gemm(a, b, algo_index, bias)        # d = a @ b (+bias)
 //   d, aux   = _C.lt_gemm_gelu(a, b, bias, algo_index)   # d = gelu(a@b+bias)
 //   dx, dbia = _C.lt_gemm_dgelu_bgrad(dy, w, aux, algo_index)
+//   dx       = _C.dgrad_tn(dy, w, algo_index)            # dx = dy @ w, TN
 //
 // algo_index < 0 uses the library heuristic (same pick as torch's
 // matmul).  a/b may be row-contiguous tensors OR transposed views of
@@ -30,6 +31,9 @@
 #include <hipblaslt/hipblaslt-ext.hpp>
 #include <hipblaslt/hipblaslt.h>
 
+#include "transpose.h"
+
+#include <cstdint>
 #include <mutex>
 #include <stdexcept>
 #include <vector>
@@ -61,6 +65,46 @@ void* lt_workspace(size_t bytes) {
 }
 
 constexpr size_t kMaxWorkspace = 128u << 20;
+
+// dgrad_tn's W^T: one grow-only buffer per device, never returned, like
+// the workspace above (at ViT-10B at most 210 MB, the fc1/fc2 weight).
+// It is taken outside the caching allocator on purpose: the step's
+// memory peak lies in the backward, a few GiB under the card's size, and
+// a transient of this size per dgrad should not pass through the
+// allocator's pools there.  Consecutive users are ordered by their
+// stream alone, so the buffer belongs to the first stream that asks;
+// nullptr sends a caller on another stream to the allocator for that
+// call.  Growing frees the old buffer, and hipFree waits for the device.
+constexpr int kMaxDevices = 16;
+
+void* wt_scratch(int device, size_t bytes, hipStream_t stream) {
+  struct Slot {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    hipStream_t owner = nullptr;
+    bool owned = false;
+  };
+  static Slot slots[kMaxDevices];
+  static std::mutex mu;
+  if (device < 0 || device >= kMaxDevices) return nullptr;
+  std::lock_guard<std::mutex> lock(mu);
+  Slot& s = slots[device];
+  if (s.owned && s.owner != stream) return nullptr;
+  if (bytes > s.bytes) {
+    if (s.ptr) (void)hipFree(s.ptr);
+    s.ptr = nullptr;
+    s.bytes = 0;
+    if (hipMalloc(&s.ptr, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      s.ptr = nullptr;
+      return nullptr;  // the caching allocator may still have room
+    }
+    s.bytes = bytes;
+  }
+  s.owner = stream;
+  s.owned = true;
+  return s.ptr;
+}
 
 // 2-D operand layout: row-contiguous (op N in the column-major dual) or
 // a transposed view of a row-contiguous base (op T).  Returns false if
@@ -209,6 +253,51 @@ torch::Tensor lt_gemm(torch::Tensor a, torch::Tensor b, long algo_index,
     mode = HIPBLASLT_EPILOGUE_BIAS;
   }
   return lt_run(a, b, algo_index, mode, bias_ptr, nullptr, "lt_gemm");
+}
+
+// dx[tok, in] = dy[tok, out] @ w[out, in], the input gradient of a
+// linear, as the library's TN form: w is transposed into W^T [in, out]
+// (csrc/transpose.hip, one read and one write of the weight) and the
+// GEMM sees it as the op-T operand, the layout of a forward x @ W^T, so
+// the tuned dual key is ("T","N", in, tok, out).  W^T is rebuilt on
+// every call: weights change every step and FSDP storage resizing makes
+// addresses recur, so nothing keyed by address would be safe to keep.
+torch::Tensor dgrad_tn(torch::Tensor dy, torch::Tensor w, long algo_index) {
+  const char* what = "dgrad_tn";
+  TORCH_CHECK(dy.is_cuda() && w.is_cuda() && dy.device() == w.device(), what,
+              ": dy and w must be on the same GPU");
+  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 &&
+                  w.scalar_type() == torch::kBFloat16,
+              what, ": bf16 only");
+  TORCH_CHECK(dy.dim() == 2 && w.dim() == 2 && dy.size(1) == w.size(0), what,
+              ": dy[tok, out] @ w[out, in] expected");
+  const int64_t tok = dy.size(0), out = w.size(0), in = w.size(1);
+  TORCH_CHECK(tok > 0 && out > 0 && in > 0, what, ": empty operand");
+  TORCH_CHECK(dy.stride(1) == 1 && dy.stride(0) == out && w.stride(1) == 1 &&
+                  w.stride(0) == in,
+              what, ": operands must be row-contiguous (no silent copy)");
+  TORCH_CHECK(in % 8 == 0 && out % 8 == 0, what,
+              ": in and out must be a multiple of 8, got in = ", in,
+              ", out = ", out);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, what,
+              ": w must be 16-byte aligned");
+  const int device = w.get_device();
+  TORCH_CHECK(device == at::cuda::current_device(), what,
+              ": operands must be on the current device");
+
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+  const size_t bytes = (size_t)in * (size_t)out * sizeof(uint16_t);
+  torch::Tensor hold;
+  void* wt = wt_scratch(device, bytes, stream);
+  if (wt == nullptr) {
+    hold = torch::empty({in, out}, w.options());
+    wt = hold.data_ptr();
+  }
+  transpose2d_launch(w.data_ptr(), wt, out, in, stream, what);
+  // W^T [in, out] contiguous, seen as its transposed view [out, in]
+  auto wt_view = torch::from_blob(wt, {out, in}, {1, out}, w.options());
+  return lt_run(dy, wt_view, algo_index, HIPBLASLT_EPILOGUE_DEFAULT, nullptr,
+                nullptr, what);
 }
 
 // d = gelu(a @ b + bias), aux = a @ b + bias (the pre-activation, saved

@@ -66,6 +66,9 @@ static std::vector<Problem> problems_vit10b() {
         {"qkv_fwd", HIPBLAS_OP_T, HIPBLAS_OP_N, qkv, tok, d},
         {"qkv_dgrad", HIPBLAS_OP_N, HIPBLAS_OP_N, d, tok, qkv},
         {"qkv_wgrad", HIPBLAS_OP_N, HIPBLAS_OP_T, d, qkv, tok},
+        // the qkv dgrad on a transposed weight (_C.dgrad_tn); the other
+        // three dgrads in that form are the fc2, fc1 and proj forwards
+        {"qkv_dgrad_tn", HIPBLAS_OP_T, HIPBLAS_OP_N, d, tok, qkv},
         {"proj_fwd", HIPBLAS_OP_T, HIPBLAS_OP_N, d, tok, d},
         {"proj_dgrad", HIPBLAS_OP_N, HIPBLAS_OP_N, d, tok, d},
         {"proj_wgrad", HIPBLAS_OP_N, HIPBLAS_OP_T, d, d, tok},

@@ -27,6 +27,9 @@
 
 #include "colsum_final.h"
 #include "common.h"
+#ifndef VITFSDP_KERNELS_ONLY
+#include "transpose.h"
+#endif
 
 namespace {
 
@@ -118,6 +121,39 @@ template __global__ void transpose_kernel<true>(const unsigned short*,
 #ifndef VITFSDP_KERNELS_ONLY
 namespace {
 
+// Grid of both kernel variants for an [R, C] input.
+struct TransposePlan {
+  dim3 grid;
+  int tpb;        // 64-row tiles per block
+  long n_chunks;  // grid.y, rows of the column-sum partials
+};
+
+TransposePlan transpose_plan(long R, long C, const char* what) {
+  const long col_tiles = (C + kTile - 1) / kTile;
+  const long row_tiles = (R + kTile - 1) / kTile;
+  // about 4096 blocks (256 CUs x 8 x 2) before a block takes more than
+  // one tile; at most 8, which keeps the partials under 1/1000 of x
+  const int tpb =
+      (int)std::min<long>(8, std::max<long>(1, row_tiles * col_tiles / 4096));
+  const long n_chunks = (row_tiles + tpb - 1) / tpb;
+  TORCH_CHECK(n_chunks <= 65535 && col_tiles < (1L << 31), what,
+              ": tensor too large");
+  return {dim3((unsigned)col_tiles, (unsigned)n_chunks), tpb, n_chunks};
+}
+
+}  // namespace
+
+void transpose2d_launch(const void* x, void* y, long R, long C,
+                        hipStream_t stream, const char* what) {
+  const TransposePlan p = transpose_plan(R, C, what);
+  hipLaunchKernelGGL(transpose_kernel<false>, p.grid, dim3(kBlock), 0, stream,
+                     (const unsigned short*)x, (unsigned short*)y,
+                     (float*)nullptr, R, C, p.tpb);
+  HIP_CHECK_LAST();
+}
+
+namespace {
+
 // x: bf16 [R, C] contiguous, C % 8 == 0.  Returns {x^T} or {x^T, colsum}.
 std::vector<torch::Tensor> transpose_run(const torch::Tensor& x, bool colsum,
                                          const char* what) {
@@ -138,28 +174,18 @@ std::vector<torch::Tensor> transpose_run(const torch::Tensor& x, bool colsum,
     return colsum ? std::vector<torch::Tensor>{y, sums}
                   : std::vector<torch::Tensor>{y};
   }
-  const long col_tiles = (C + kTile - 1) / kTile;
-  const long row_tiles = (R + kTile - 1) / kTile;
-  // about 4096 blocks (256 CUs x 8 x 2) before a block takes more than
-  // one tile; at most 8, which keeps the partials under 1/1000 of x
-  const int tpb =
-      (int)std::min<long>(8, std::max<long>(1, row_tiles * col_tiles / 4096));
-  const long n_chunks = (row_tiles + tpb - 1) / tpb;
-  TORCH_CHECK(n_chunks <= 65535 && col_tiles < (1L << 31), what,
-              ": tensor too large");
   auto stream = at::cuda::getCurrentCUDAStream();
-  const dim3 grid((unsigned)col_tiles, (unsigned)n_chunks);
-  auto* xp = (const unsigned short*)x.data_ptr();
-  auto* yp = (unsigned short*)y.data_ptr();
   if (!colsum) {
-    hipLaunchKernelGGL(transpose_kernel<false>, grid, dim3(kBlock), 0, stream,
-                       xp, yp, (float*)nullptr, R, C, tpb);
-    HIP_CHECK_LAST();
+    transpose2d_launch(x.data_ptr(), y.data_ptr(), R, C, stream, what);
     return {y};
   }
+  const TransposePlan p = transpose_plan(R, C, what);
+  const long n_chunks = p.n_chunks;
+  auto* xp = (const unsigned short*)x.data_ptr();
+  auto* yp = (unsigned short*)y.data_ptr();
   auto part = torch::empty({n_chunks, C}, x.options().dtype(torch::kFloat32));
-  hipLaunchKernelGGL(transpose_kernel<true>, grid, dim3(kBlock), 0, stream, xp,
-                     yp, part.data_ptr<float>(), R, C, tpb);
+  hipLaunchKernelGGL(transpose_kernel<true>, p.grid, dim3(kBlock), 0, stream,
+                     xp, yp, part.data_ptr<float>(), R, C, p.tpb);
   HIP_CHECK_LAST();
   hipLaunchKernelGGL(colsum_final_kernel, colsum_final_grid(C),
                      dim3(kColsumFinalBlock), 0, stream,

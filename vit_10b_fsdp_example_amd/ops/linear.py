@@ -1,7 +1,9 @@
 """Linear layer with a native weight-gradient kernel.
 
 Forward and the input-gradient GEMM go through hipBLASLt (the sanctioned
-library path for plain GEMMs); the weight gradient dW = dY^T X routes
+library path for plain GEMMs; the input gradient as its TN kernel on a
+weight transposed by csrc/transpose.hip, see "Input gradients as library
+TN GEMMs" below); the weight gradient dW = dY^T X routes
 through csrc/wgemm.hip (gfx950 ds_read_b64_tr_b16 hardware transpose
 reads on direct-to-LDS staged tiles) for the shapes where that kernel
 beats the library INSIDE the training step.
@@ -235,6 +237,64 @@ def _tn_wgrad_out_ok(m, k):
     return k >= _TN_WGRAD_MIN_K and any(m == s[0] for s in _TN_WGRAD_SHAPES)
 
 
+# --------------------------------------------------------------------------
+# Input gradients as library TN GEMMs on a transposed weight
+# (_C.dgrad_tn, csrc/ltgemm.cpp + csrc/transpose.hip).  dX[tok, in] =
+# dY[tok, out] W[out, in] is the library's NN form; with W^T [in, out]
+# as a contiguous tensor it is the TN form of a forward, which the step
+# trace shows 13-15 % faster per FLOP.  Only the weight is transposed:
+# 52-210 MB read and written once per call against a 5-7 TFLOP GEMM.
+# The route answers AddmmBackward's mm(dy, W), both operands
+# row-contiguous; W^T lives in a scratch buffer of the extension and is
+# rebuilt on every call (weights change every step).
+#
+# MI355X, 32768 token rows, us per call (benchmarks/bench_tn_dgrad.py,
+# isolated with cold-cache rotation, parent / new builds alternated;
+# step columns from kernel traces of both; profiles/PROFILES.md
+# "TN dgrad"):
+#
+#     weight (out x in)    isolated                  in the ViT-10B step
+#                          NN      W^T + TN          NN      W^T + TN
+#     qkv  15360 x 5120    3868    3399   routed     3655    55 + 3090
+#     proj  5120 x 5120    1294    1185   routed     1363    24 + 1188
+#     fc1  20480 x 5120    5212    4582   routed     5029    97 + 4363
+#     fc2   5120 x 20480   5358    5068   routed     5040    99 + 4839
+#
+# -1.33 ms per block, 1831 -> 1792 ms/step end to end.  The TN index is
+# the tabled one of the forward with the same sizes (fc2, fc1 and proj
+# forwards); qkv's key ("T","N", 5120, tok, 15360) has no entry and takes
+# the library heuristic, which no searched index beats on cold caches.
+# VITFSDP_TN_DGRAD=0 turns the route off.
+# --------------------------------------------------------------------------
+
+# (out, in) of the weights whose dgrad won both isolated and in the step
+_TN_DGRAD_SHAPES = frozenset(
+    {(15360, 5120), (5120, 5120), (20480, 5120), (5120, 20480)})
+
+# Measured at 32768 token rows.  The weight transpose does not shrink
+# with the batch while the GEMM does, so the route keeps away from short
+# GEMMs (the same floor as _TN_WGRAD_MIN_K).
+_TN_DGRAD_MIN_TOK = 4096
+
+# Experiments and tests: when >= 0, every dgrad whose weight has at least
+# this many elements is routed whatever the table and the floor say.
+_TN_DGRAD_MIN_ELEMS = int(os.environ.get("VITFSDP_TN_DGRAD_MIN_ELEMS", "-1"))
+
+
+def _tn_dgrad_on():
+    return os.environ.get("VITFSDP_TN_DGRAD", "1") != "0"
+
+
+def _tn_dgrad_shapes_ok(out, inn, tok):
+    """Shape gate of the TN dgrad route for dy [tok, out] @ W [out, in].
+    _C.dgrad_tn needs both weight dimensions to be multiples of 8."""
+    if out % 8 or inn % 8:
+        return False
+    if _TN_DGRAD_MIN_ELEMS >= 0:
+        return out * inn >= _TN_DGRAD_MIN_ELEMS
+    return (out, inn) in _TN_DGRAD_SHAPES and tok >= _TN_DGRAD_MIN_TOK
+
+
 def _same_buffer(t, ref):
     """t is the tensor ref or a same-sized contiguous view of it whose
     rows have ref's length (the identity test of the parked sums)."""
@@ -419,12 +479,14 @@ class TunedGemmMode(TorchDispatchMode):
 
     Also hosts the native-wgrad reroute when VITFSDP_NATIVE_WGRAD=2, the
     TN weight-gradient route (which takes precedence at the shapes in
-    its gate) and the fused MLP GELU epilogues when configured, so one
-    mode covers the whole step (push around forward AND backward).
+    its gate), the TN input-gradient route (_C.dgrad_tn, ahead of the
+    tuned N,N index at the shapes in its gate) and the fused MLP GELU
+    epilogues when configured, so one mode covers the whole step (push
+    around forward AND backward).
     """
 
     def __init__(self, table=None, native_wgrad=None, handler=None,
-                 dgelu_handler=None, tn_handler=None):
+                 dgelu_handler=None, tn_handler=None, dgrad_handler=None):
         super().__init__()
         self.table = lt_algo_table() if table is None else table
         self.native_wgrad = (
@@ -472,6 +534,14 @@ class TunedGemmMode(TorchDispatchMode):
         self._tn_mm_first = False
         self.tn_hits = 0
         self.tn_dbias_hits = 0
+        # TN input gradients (see module comment above).
+        # test seam: dgrad_handler(dy, w, idx) -> dx replaces
+        # _C.dgrad_tn and lifts the CUDA/bf16 gate
+        self._dgrad_handler = dgrad_handler
+        self.tn_dgrad = _tn_dgrad_on() and (
+            dgrad_handler is not None or self._handler is None
+        )
+        self.tn_dgrad_hits = 0
 
     def __exit__(self, exc_type, exc_val, exc_tb):
         self._dgelu_stash = None
@@ -664,6 +734,40 @@ class TunedGemmMode(TorchDispatchMode):
             return colsum.view([1] * (t.dim() - 1) + [t.shape[-1]])
         return colsum
 
+    # -- TN input-gradient helpers -------------------------------------------
+
+    def _is_tn_dgrad_mm(self, dy, w):
+        """mm(dy [tok, out], W [out, in]) with both operands row-contiguous
+        (a weight gradient's first operand is a transposed view, a
+        forward's second one is), at a gated shape, and nothing that
+        _C.dgrad_tn would refuse."""
+        if _op_layout(dy) != "N" or _op_layout(w) != "N":
+            return False
+        if dy.shape[1] != w.shape[0] or w.data_ptr() % 16:
+            return False
+        if not _tn_dgrad_shapes_ok(w.shape[0], w.shape[1], dy.shape[0]):
+            return False
+        if self._dgrad_handler is not None:
+            return True
+        return (
+            w.is_cuda and w.dtype == torch.bfloat16
+            and dy.dtype == torch.bfloat16 and dy.device == w.device
+        )
+
+    def _tn_dgrad(self, dy, w):
+        """dx = dy @ W as the TN GEMM on W^T, which _C.dgrad_tn writes
+        and drops.  That GEMM is lt_gemm(dy, wT.t()), so its tuned index
+        is the one under the dual key of a forward with these sizes."""
+        out, inn = w.shape
+        idx = self.table.get(("T", "N", inn, dy.shape[0], out)) \
+            if self.table else None
+        idx = -1 if idx is None else idx
+        self.tn_dgrad_hits += 1
+        if self._dgrad_handler is not None:
+            return self._dgrad_handler(dy, w, idx)
+        # a missing kernel is an error here, not a fallback
+        return ext().dgrad_tn(dy, w, idx)
+
     def __torch_dispatch__(self, func, types, args=(), kwargs=None):
         kwargs = kwargs or {}
         if func is torch.ops.aten.mm.default and self._gpu_ok(args[0]):
@@ -680,6 +784,8 @@ class TunedGemmMode(TorchDispatchMode):
                 (dw,) = ext().wgrad_gemm(a.t().contiguous(), b.contiguous(),
                                          False)
                 return dw
+            if self.tn_dgrad and self._is_tn_dgrad_mm(a, b):
+                return self._tn_dgrad(a, b)
             idx = self._tuned_index(a, b)
             if idx is not None:
                 self.hits += 1
