@@ -47,10 +47,15 @@ struct TensorTable {
 
 template <bool GRAD_BF16>
 __global__ void fused_adamw_kernel(AdamWTable tab, float lr, float beta1,
-                                   float beta2, float eps, float wd,
-                                   float bias_c1, float bias_c2,
+                                   float beta2, float omb1, float omb2,
+                                   float eps, float wd, float bias_c1,
+                                   float bias_c2,
                                    const float* __restrict__ grad_scale,
                                    float prescale) {
+  // omb1 / omb2 are 1 - beta1 / 1 - beta2 formed in double on the host
+  // (as torch.optim.AdamW forms them): 1.f - 0.999f is 1.3e-5 relative
+  // below 1 - 0.999, and at step 1 all of v would carry that error.
+  //
   // deferred gradient clipping + mean divide: the clip coefficient (a
   // device scalar from clip_grad_norm_(defer_scale=True)) and the
   // 1/world_size prescale scale g on the fly, replacing separate full
@@ -82,8 +87,8 @@ __global__ void fused_adamw_kernel(AdamWTable tab, float lr, float beta1,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float pj = (&pv.x)[j], gj = gj4[j] * gs;
-        float mj = beta1 * (&mv.x)[j] + (1.f - beta1) * gj;
-        float vj = beta2 * (&vv.x)[j] + (1.f - beta2) * gj * gj;
+        float mj = beta1 * (&mv.x)[j] + omb1 * gj;
+        float vj = beta2 * (&vv.x)[j] + omb2 * gj * gj;
         pj *= decay;
         pj -= step_size * mj / (sqrtf(vj) * inv_sqrt_c2 + eps);
         (&pv.x)[j] = pj;
@@ -112,8 +117,8 @@ __global__ void fused_adamw_kernel(AdamWTable tab, float lr, float beta1,
                            : ((const float*)tab.g[ti])[i];
       gj *= gs;
       float pj = tab.p[ti][i];
-      float mj = beta1 * tab.m[ti][i] + (1.f - beta1) * gj;
-      float vj = beta2 * tab.v[ti][i] + (1.f - beta2) * gj * gj;
+      float mj = beta1 * tab.m[ti][i] + omb1 * gj;
+      float vj = beta2 * tab.v[ti][i] + omb2 * gj * gj;
       pj = pj * decay - step_size * mj / (sqrtf(vj) * inv_sqrt_c2 + eps);
       tab.p[ti][i] = pj;
       tab.m[ti][i] = mj;
@@ -237,10 +242,49 @@ void fused_adamw(std::vector<torch::Tensor> params,
   }
   auto stream = at::cuda::getCurrentCUDAStream();
   const int n = (int)params.size();
+  TORCH_CHECK(grads.size() == params.size() &&
+                  exp_avgs.size() == params.size() &&
+                  exp_avg_sqs.size() == params.size(),
+              "fused_adamw: params, grads, exp_avgs and exp_avg_sqs must have "
+              "one length");
   if (n == 0) return;
   const auto grad_dtype = grads[0].scalar_type();
   TORCH_CHECK(grad_dtype == torch::kFloat32 || grad_dtype == torch::kBFloat16,
               "fused_adamw: grads must be fp32 or bf16");
+  const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
+  // validate every tensor before the first launch: a bad entry in a later
+  // table must not leave the earlier ones stepped
+  for (int i = 0; i < n; ++i) {
+    auto& p = params[i];
+    auto& g = grads[i];
+    TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
+                    p.is_contiguous(),
+                "fused_adamw expects contiguous fp32 CUDA tensors");
+    TORCH_CHECK(g.device() == p.device() && g.scalar_type() == grad_dtype &&
+                    g.is_contiguous() && g.numel() >= p.numel(),
+                "fused_adamw: grads must share one dtype and the param's "
+                "device and cover params");
+    const torch::Tensor* states[2] = {&exp_avgs[i], &exp_avg_sqs[i]};
+    for (int k = 0; k < 2; ++k) {
+      const auto& st = *states[k];
+      const char* name = k == 0 ? "exp_avg" : "exp_avg_sq";
+      TORCH_CHECK(st.device() == p.device(), "fused_adamw: ", name,
+                  " must be on the param's device");
+      TORCH_CHECK(st.scalar_type() == torch::kFloat32, "fused_adamw: ", name,
+                  " must be fp32, got ", st.scalar_type());
+      TORCH_CHECK(st.numel() == p.numel(), "fused_adamw: ", name, " must have ",
+                  p.numel(), " elements like its param, got ", st.numel());
+      TORCH_CHECK(st.is_contiguous(), "fused_adamw: ", name,
+                  " must be contiguous");
+    }
+    if (!mirrors.empty() && mirrors[i].has_value()) {
+      auto& mt = *mirrors[i];
+      TORCH_CHECK(mt.device() == p.device() &&
+                      mt.scalar_type() == torch::kBFloat16 &&
+                      mt.numel() == p.numel() && mt.is_contiguous(),
+                  "mirror must be a contiguous bf16 tensor of p's size");
+    }
+  }
   for (int base = 0; base < n; base += kMaxTensors) {
     AdamWTable tab;
     tab.count = std::min(kMaxTensors, n - base);
@@ -248,12 +292,6 @@ void fused_adamw(std::vector<torch::Tensor> params,
     for (int i = 0; i < tab.count; ++i) {
       auto& p = params[base + i];
       auto& g = grads[base + i];
-      TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
-                      p.is_contiguous(),
-                  "fused_adamw expects contiguous fp32 CUDA tensors");
-      TORCH_CHECK(g.scalar_type() == grad_dtype && g.is_contiguous() &&
-                      g.numel() >= p.numel(),
-                  "fused_adamw: grads must share one dtype and cover params");
       tab.p[i] = p.data_ptr<float>();
       tab.g[i] = g.data_ptr();
       tab.m[i] = exp_avgs[base + i].data_ptr<float>();
@@ -261,9 +299,6 @@ void fused_adamw(std::vector<torch::Tensor> params,
       tab.mir[i] = nullptr;
       if (!mirrors.empty() && mirrors[base + i].has_value()) {
         auto& mt = *mirrors[base + i];
-        TORCH_CHECK(mt.scalar_type() == torch::kBFloat16 &&
-                        mt.numel() == p.numel() && mt.is_contiguous(),
-                    "mirror must be a contiguous bf16 tensor of p's size");
         tab.mir[i] = (unsigned short*)mt.data_ptr();
       }
       tab.n[i] = p.numel();
@@ -272,13 +307,15 @@ void fused_adamw(std::vector<torch::Tensor> params,
     if (grad_dtype == torch::kBFloat16) {
       hipLaunchKernelGGL(fused_adamw_kernel<true>, dim3(grid_for(total)),
                          dim3(kBlock), 0, stream, tab, (float)lr, (float)beta1,
-                         (float)beta2, (float)eps, (float)weight_decay,
+                         (float)beta2, omb1, omb2, (float)eps,
+                         (float)weight_decay,
                          (float)bias_c1, (float)bias_c2, gs_ptr,
                          (float)grad_prescale);
     } else {
       hipLaunchKernelGGL(fused_adamw_kernel<false>, dim3(grid_for(total)),
                          dim3(kBlock), 0, stream, tab, (float)lr, (float)beta1,
-                         (float)beta2, (float)eps, (float)weight_decay,
+                         (float)beta2, omb1, omb2, (float)eps,
+                         (float)weight_decay,
                          (float)bias_c1, (float)bias_c2, gs_ptr,
                          (float)grad_prescale);
     }
@@ -328,6 +365,9 @@ void mt_dispatch(std::vector<torch::Tensor>& tensors, const char* what,
 }  // namespace
 
 torch::Tensor multi_tensor_sqnorm(std::vector<torch::Tensor> tensors) {
+  TORCH_CHECK(!tensors.empty(),
+              "multi_tensor_sqnorm: empty tensor list (no device to put the "
+              "result on)");
   auto stream = at::cuda::getCurrentCUDAStream();
   auto out = torch::zeros({}, tensors[0].options().dtype(torch::kFloat32));
   float* out_ptr = out.data_ptr<float>();

@@ -9,6 +9,8 @@
 #include <torch/extension.h>
 #endif
 
+#include <climits>
+
 #include "common.h"
 
 namespace {
@@ -65,12 +67,35 @@ __global__ void ce_bwd_kernel(const unsigned short* __restrict__ logits,
 }  // namespace
 
 #ifndef VITFSDP_KERNELS_ONLY
+namespace {
+
+// The kernels index raw pointers by the shape of logits alone, so every
+// operand is checked against it before a launch.  An empty batch is
+// refused: its mean loss is 0/0 and there is no row to launch a block for.
+void check_logits_target(const char* fn, const torch::Tensor& logits,
+                         const torch::Tensor& target) {
+  TORCH_CHECK(logits.is_cuda(), fn, ": logits must be a GPU tensor");
+  TORCH_CHECK(logits.scalar_type() == torch::kBFloat16, fn,
+              ": logits must be bf16, got ", logits.scalar_type());
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0 && logits.size(1) > 0 &&
+                  logits.size(1) <= INT_MAX,
+              fn, ": logits must be a non-empty [N, C], got ", logits.sizes());
+  TORCH_CHECK(logits.is_contiguous(), fn, ": logits must be contiguous");
+  TORCH_CHECK(target.is_cuda() && target.device() == logits.device(), fn,
+              ": target must be a GPU tensor on the device of logits");
+  TORCH_CHECK(target.scalar_type() == torch::kLong, fn,
+              ": target must be int64, got ", target.scalar_type());
+  TORCH_CHECK(target.dim() == 1 && target.size(0) == logits.size(0), fn,
+              ": target must have shape [N] = [", logits.size(0), "], got ",
+              target.sizes());
+  TORCH_CHECK(target.is_contiguous(), fn, ": target must be contiguous");
+}
+
+}  // namespace
+
 std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
                                              torch::Tensor target) {
-  TORCH_CHECK(logits.is_cuda() && logits.is_contiguous() && logits.dim() == 2);
-  TORCH_CHECK(logits.scalar_type() == torch::kBFloat16,
-              "cross_entropy_fwd: bf16 logits only");
-  TORCH_CHECK(target.scalar_type() == torch::kLong);
+  check_logits_target("cross_entropy_fwd", logits, target);
   const long n = logits.size(0);
   const int c = (int)logits.size(1);
   auto opts = logits.options().dtype(torch::kFloat32);
@@ -87,10 +112,26 @@ std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
 
 torch::Tensor cross_entropy_bwd(torch::Tensor dloss, torch::Tensor logits,
                                 torch::Tensor target, torch::Tensor lse) {
+  const char* fn = "cross_entropy_bwd";
+  check_logits_target(fn, logits, target);
   const long n = logits.size(0);
   const int c = (int)logits.size(1);
+  TORCH_CHECK(lse.is_cuda() && lse.device() == logits.device(), fn,
+              ": lse must be a GPU tensor on the device of logits");
+  TORCH_CHECK(lse.scalar_type() == torch::kFloat32, fn,
+              ": lse must be fp32, got ", lse.scalar_type());
+  TORCH_CHECK(lse.dim() == 1 && lse.size(0) == n, fn,
+              ": lse must have shape [N] = [", n, "], got ", lse.sizes());
+  TORCH_CHECK(lse.is_contiguous(), fn, ": lse must be contiguous");
+  TORCH_CHECK(dloss.is_cuda() && dloss.device() == logits.device(), fn,
+              ": dloss must be a GPU tensor on the device of logits");
+  TORCH_CHECK(dloss.scalar_type() == torch::kFloat32, fn,
+              ": dloss must be fp32 like the loss, got ", dloss.scalar_type());
+  TORCH_CHECK(dloss.numel() == 1, fn, ": dloss must hold one element, got ",
+              dloss.sizes());
   auto dlogits = torch::empty_like(logits);
-  auto dloss_f = dloss.to(torch::kFloat32);
+  // one element, but possibly a view with a storage offset or stride
+  auto dloss_f = dloss.contiguous();
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)n), dim3(kBlock), 0, stream,
                      (const unsigned short*)logits.data_ptr(),

@@ -496,19 +496,73 @@ inline bool fused_bwd_fits(int d) {
   return d % 8 == 0 && d / 8 <= kMaxVpt * kBlock;
 }
 
+// Operand checks.  The kernels read raw bf16 / fp32 pointers with sizes
+// taken from x alone, so every other operand is checked against x before
+// a launch: a wrong dtype would be reinterpreted, a short tensor read
+// out of bounds.
+
+// the [rows, D] input that fixes D, the row count and the device
+void check_rows_input(const char* fn, const char* name,
+                      const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), fn, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, fn, ": ", name,
+              " must be bf16, got ", x.scalar_type());
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0 && x.size(-1) % 8 == 0, fn,
+              ": ", name, " must have a last dimension D that is a positive "
+              "multiple of 8, got shape ", x.sizes());
+  TORCH_CHECK(x.is_contiguous(), fn, ": ", name, " must be contiguous");
+}
+
+// another [rows, D] bf16 operand: dy, dsum, res
+void check_rows_like(const char* fn, const char* name, const torch::Tensor& t,
+                     const torch::Tensor& x) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device(), fn, ": ", name,
+              " must be a GPU tensor on the device of the other operands");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, fn, ": ", name,
+              " must be bf16, got ", t.scalar_type());
+  TORCH_CHECK(t.sizes() == x.sizes(), fn, ": ", name, " must have shape ",
+              x.sizes(), ", got ", t.sizes());
+  TORCH_CHECK(t.is_contiguous(), fn, ": ", name, " must be contiguous");
+}
+
+// gamma / beta: bf16 of D elements
+void check_affine(const char* fn, const char* name, const torch::Tensor& t,
+                  const torch::Tensor& x) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device(), fn, ": ", name,
+              " must be a GPU tensor on the device of the other operands");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, fn, ": ", name,
+              " must be bf16, got ", t.scalar_type());
+  TORCH_CHECK(t.numel() == x.size(-1), fn, ": ", name, " must have D = ",
+              x.size(-1), " elements, got ", t.numel());
+  TORCH_CHECK(t.is_contiguous(), fn, ": ", name, " must be contiguous");
+}
+
+// saved mean / rstd: fp32, one per row
+void check_stat(const char* fn, const char* name, const torch::Tensor& t,
+                const torch::Tensor& x, long rows) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device(), fn, ": ", name,
+              " must be a GPU tensor on the device of the other operands");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, fn, ": ", name,
+              " must be fp32, got ", t.scalar_type());
+  TORCH_CHECK(t.numel() == rows, fn, ": ", name, " must have one element per "
+              "row (", rows, "), got ", t.numel());
+  TORCH_CHECK(t.is_contiguous(), fn, ": ", name, " must be contiguous");
+}
+
 }  // namespace
 
 std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
                                          torch::Tensor b, double eps) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "layernorm_fwd: bf16 only");
+  check_rows_input("layernorm_fwd", "x", x);
+  check_affine("layernorm_fwd", "weight", w, x);
+  check_affine("layernorm_fwd", "bias", b, x);
   const int d = x.size(-1);
-  TORCH_CHECK(d % 8 == 0, "layernorm_fwd: D must be a multiple of 8");
   const long n = x.numel() / d;
   auto y = torch::empty_like(x);
   auto opts = x.options().dtype(torch::kFloat32);
   auto mean = torch::empty({n}, opts);
   auto rstd = torch::empty({n}, opts);
+  if (n == 0) return {y, mean, rstd};  // a zero-sized grid is a launch error
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)n), dim3(kBlock), 0, stream,
                      (const ushort8_t*)x.data_ptr(),
@@ -523,9 +577,13 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
 std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
                                          torch::Tensor w, torch::Tensor mean,
                                          torch::Tensor rstd) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && x.is_contiguous());
+  check_rows_input("layernorm_bwd", "x", x);
+  check_rows_like("layernorm_bwd", "dy", dy, x);
+  check_affine("layernorm_bwd", "weight", w, x);
   const int d = x.size(-1);
   const long n = x.numel() / d;
+  check_stat("layernorm_bwd", "mean", mean, x, n);
+  check_stat("layernorm_bwd", "rstd", rstd, x, n);
   auto dx = torch::empty_like(x);
   auto dw = torch::empty_like(w);
   auto db = torch::empty_like(w);
@@ -556,16 +614,18 @@ std::vector<torch::Tensor> layernorm_add_fwd(torch::Tensor x,
                                              torch::Tensor res,
                                              torch::Tensor w, torch::Tensor b,
                                              double eps) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && res.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "bf16 only");
+  check_rows_input("layernorm_add_fwd", "x", x);
+  check_rows_like("layernorm_add_fwd", "res", res, x);
+  check_affine("layernorm_add_fwd", "weight", w, x);
+  check_affine("layernorm_add_fwd", "bias", b, x);
   const int d = x.size(-1);
-  TORCH_CHECK(d % 8 == 0, "layernorm_add_fwd: D must be a multiple of 8");
   const long n = x.numel() / d;
   auto sum = torch::empty_like(x);
   auto y = torch::empty_like(x);
   auto opts = x.options().dtype(torch::kFloat32);
   auto mean = torch::empty({n}, opts);
   auto rstd = torch::empty({n}, opts);
+  if (n == 0) return {sum, y, mean, rstd};
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(ln_add_fwd_kernel, dim3((unsigned)n), dim3(kBlock), 0,
                      stream, (const ushort8_t*)x.data_ptr(),
@@ -585,10 +645,14 @@ std::vector<torch::Tensor> layernorm_add_bwd(torch::Tensor dy,
                                              torch::Tensor w,
                                              torch::Tensor mean,
                                              torch::Tensor rstd) {
-  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dsum.is_contiguous() &&
-              sum.is_contiguous());
+  check_rows_input("layernorm_add_bwd", "sum", sum);
+  check_rows_like("layernorm_add_bwd", "dy", dy, sum);
+  check_rows_like("layernorm_add_bwd", "dsum", dsum, sum);
+  check_affine("layernorm_add_bwd", "weight", w, sum);
   const int d = sum.size(-1);
   const long n = sum.numel() / d;
+  check_stat("layernorm_add_bwd", "mean", mean, sum, n);
+  check_stat("layernorm_add_bwd", "rstd", rstd, sum, n);
   auto dx1 = torch::empty_like(sum);
   auto dx2 = torch::empty_like(sum);
   auto dw = torch::empty_like(w);

@@ -29,11 +29,28 @@ class _LayerNormFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+def _kernel_operands(x, weight, bias):
+    """The HIP kernels read x, gamma and beta as bf16 rows of D = a
+    multiple of 8 elements.  Anything else (fp32 debug/parity mode, an
+    fp32 gamma next to a bf16 x, no affine parameters) takes the framework
+    op: the kernels refuse it, and must never reinterpret it."""
+    return (
+        x.dtype == torch.bfloat16
+        and x.dim() >= 1
+        and x.shape[-1] > 0
+        and x.shape[-1] % 8 == 0
+        and weight is not None
+        and bias is not None
+        and weight.dtype == torch.bfloat16
+        and bias.dtype == torch.bfloat16
+    )
+
+
 def layer_norm(x, weight, bias, eps=1e-6):
-    # the HIP kernel is the bf16 path; fp32 (debug/parity mode) uses the
-    # framework op on either device
-    if x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 and use_hip(x):
-        return _LayerNormFn.apply(x.contiguous(), weight, bias, eps)
+    if _kernel_operands(x, weight, bias) and use_hip(x, weight, bias):
+        return _LayerNormFn.apply(
+            x.contiguous(), weight.contiguous(), bias.contiguous(), eps
+        )
     return F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
 
 
@@ -63,12 +80,14 @@ def fused_add_layer_norm(x, res, weight, bias, eps=1e-6):
     no separate elementwise add kernels run in either direction.
     """
     if (
-        x.dtype == torch.bfloat16
-        and x.shape[-1] % 8 == 0
-        and use_hip(x, res)
+        _kernel_operands(x, weight, bias)
+        and res.dtype == torch.bfloat16
+        and res.shape == x.shape
+        and use_hip(x, res, weight, bias)
     ):
         return _FusedAddLayerNormFn.apply(
-            x.contiguous(), res.contiguous(), weight, bias, eps
+            x.contiguous(), res.contiguous(), weight.contiguous(),
+            bias.contiguous(), eps
         )
     s = x + res
     return s, F.layer_norm(s, (s.shape[-1],), weight, bias, eps)
