@@ -6,7 +6,6 @@ from .adamw import FusedAdamW
 from .multi_tensor import local_sqnorm, scale_
 from .linear import (
     NativeLinear, NativeWgradMode, TunedGemmMode, gemm_dispatch_context,
-    wgrad_backward_context,
 )
 from .dropout import (
     HiddenDropout, dropout_add, dropout_add_reference, gelu_dropout,
@@ -33,7 +32,6 @@ __all__ = [
     "NativeWgradMode",
     "TunedGemmMode",
     "gemm_dispatch_context",
-    "wgrad_backward_context",
     "HiddenDropout",
     "hidden_dropout",
     "dropout_add",

@@ -8,26 +8,14 @@ through csrc/wgemm.hip (gfx950 ds_read_b64_tr_b16 hardware transpose
 reads on direct-to-LDS staged tiles) for the shapes where that kernel
 beats the library INSIDE the training step.
 
-Where the kernel stands (MI355X, K = 32768; receipts and the rung-by-rung
-table in profiles/PROFILES.md "wgemm NT ladder"):
-
-    shape (M=out, N=in)     isolated, cold cache    in the ViT-10B step
-                            first    now            now    library
-    qkv   15360 x 5120      5.36     4.48 ms        4.64   5.09 ms   routed
-    proj   5120 x 5120      1.97     1.64           1.78   1.96      routed
-    fc1   20480 x 5120      7.66     6.43           6.41   6.29      library TN
-    fc2    5120 x 20480     7.46     6.56           6.45   6.24      library TN
-
-("first" is the register-staged first version of the kernel; all
-columns from one machine, the library in-step times from a trace of
-the step with the route off.)  "library TN": fc1 and fc2 no longer run
-the library's NT kernel either; they run its TN kernel on operands
-transposed by csrc/transpose.hip (the "TN weight gradients" section
-below: 5.2-5.4 ms per call with both transposes and the bias sums,
-VITFSDP_TN_WGRAD).  The default route,
-VITFSDP_NATIVE_WGRAD=2, is the dispatcher-level interception below
-(NativeWgradMode, or the native_wgrad branch of TunedGemmMode); the
-shape gate _wgrad_mm_shapes_ok keeps fc1/fc2 on the library.
+The kernel beats the library in the step on the qkv and proj shapes and
+loses on fc1 and fc2, which run the library's TN kernel on operands
+transposed by csrc/transpose.hip instead (the "TN weight gradients"
+section below, VITFSDP_TN_WGRAD); measurements per shape, isolated and
+in the step, in profiles/PROFILES.md "wgemm NT ladder".  The default
+route, VITFSDP_NATIVE_WGRAD=2, is the dispatcher-level interception
+below (NativeWgradMode, or the wgemm route of TunedGemmMode); the shape
+gate _wgrad_mm_shapes_ok keeps fc1/fc2 away from the kernel.
 VITFSDP_NATIVE_WGRAD=0 switches the route off.
 
 How the integration got here (all measured on MI355X):
@@ -176,22 +164,14 @@ def _is_wgrad_mm(at, b):
 # so the separate reduction goes too.  AddmmBackward on this torch emits
 #     mm(dy, W) ; mm(dy.t(), x) -> [out, in] ; sum.dim_IntList(dy, [0], True)
 # and the route answers the second and third; either may come first.
+# fc1's dy^T is a third output of the GELU backward
+# (_C.gelu_bwd_colsum_t, VITFSDP_TN_DGELU_T).
 #
-# MI355X, K = 32768, ms per call, isolated with cold-cache rotation
-# (benchmarks/bench_tn_wgrad.py; profiles/PROFILES.md "TN wgrad"):
-#
-#     shape (out x in)     NT GEMM + sum       TN GEMM   transposes + TN
-#     fc1  20480 x 5120    6.29 + 0.24         4.68      5.23    routed
-#     fc2   5120 x 20480   6.30 + 0.07         4.80      5.41    routed
-#     qkv  15360 x 5120    4.53 + 0.18         4.02      4.48    wgemm.hip
-#     proj  5120 x 5120    1.61 + 0.07         1.81      2.12    wgemm.hip
-#
-# In the step fc1 and fc2 gain 1.17 and 1.03 ms per call (1927 -> 1864
-# ms/step); fc1's dy^T is a third output of the GELU backward
-# (_C.gelu_bwd_colsum_t, VITFSDP_TN_DGELU_T).  qkv gains 0.38 ms per call in the step trace, but isolated
-# on one machine it leads the wgemm.hip path by 1-3 % only, inside the spread
-# of the parent's own samples, so it stays on wgemm.hip.
-# VITFSDP_TN_WGRAD=0 turns the route off.
+# Gate: the shapes that won both isolated and in the step, fc1 and fc2
+# (_TN_WGRAD_SHAPES); proj loses and qkv leads the wgemm.hip path by less
+# than the spread of its own samples, so both stay there.
+# VITFSDP_TN_WGRAD=0 turns the route off.  Measurements:
+# benchmarks/bench_tn_wgrad.py, profiles/PROFILES.md "TN wgrad".
 # --------------------------------------------------------------------------
 
 # (out, in) of the dW shapes that won both isolated and in the step
@@ -237,6 +217,12 @@ def _tn_wgrad_out_ok(m, k):
     return k >= _TN_WGRAD_MIN_K and any(m == s[0] for s in _TN_WGRAD_SHAPES)
 
 
+def _is_tn_wgrad_mm(at, b):
+    """The weight-gradient GEMM, at a shape the TN route takes."""
+    dims = _wgrad_mm_dims(at, b)
+    return dims is not None and _tn_wgrad_shapes_ok(*dims)
+
+
 # --------------------------------------------------------------------------
 # Input gradients as library TN GEMMs on a transposed weight
 # (_C.dgrad_tn, csrc/ltgemm.cpp + csrc/transpose.hip).  dX[tok, in] =
@@ -248,23 +234,13 @@ def _tn_wgrad_out_ok(m, k):
 # row-contiguous; W^T lives in a scratch buffer of the extension and is
 # rebuilt on every call (weights change every step).
 #
-# MI355X, 32768 token rows, us per call (benchmarks/bench_tn_dgrad.py,
-# isolated with cold-cache rotation, parent / new builds alternated;
-# step columns from kernel traces of both; profiles/PROFILES.md
-# "TN dgrad"):
-#
-#     weight (out x in)    isolated                  in the ViT-10B step
-#                          NN      W^T + TN          NN      W^T + TN
-#     qkv  15360 x 5120    3868    3399   routed     3655    55 + 3090
-#     proj  5120 x 5120    1294    1185   routed     1363    24 + 1188
-#     fc1  20480 x 5120    5212    4582   routed     5029    97 + 4363
-#     fc2   5120 x 20480   5358    5068   routed     5040    99 + 4839
-#
-# -1.33 ms per block, 1831 -> 1792 ms/step end to end.  The TN index is
-# the tabled one of the forward with the same sizes (fc2, fc1 and proj
-# forwards); qkv's key ("T","N", 5120, tok, 15360) has no entry and takes
-# the library heuristic, which no searched index beats on cold caches.
-# VITFSDP_TN_DGRAD=0 turns the route off.
+# The TN index is the tabled one of the forward with the same sizes (fc2,
+# fc1 and proj forwards); qkv's key ("T","N", 5120, tok, 15360) has no
+# entry and takes the library heuristic, which no searched index beats on
+# cold caches.  Gate: all four weights of the block won isolated and in
+# the step (_TN_DGRAD_SHAPES).  VITFSDP_TN_DGRAD=0 turns the route off.
+# Measurements: benchmarks/bench_tn_dgrad.py, profiles/PROFILES.md
+# "TN dgrad".
 # --------------------------------------------------------------------------
 
 # (out, in) of the weights whose dgrad won both isolated and in the step
@@ -329,6 +305,41 @@ def _row_sum_args(args, kwargs):
     return t, keepdim
 
 
+def _hip_bf16(*tensors):
+    """The GPU gate of both modes and every route below: all of these
+    are bf16 tensors on one GPU and the extension serves them (use_hip
+    raises when it is not built, so that a GPU step cannot quietly run
+    without it).
+
+    It asks more than any of the four hand-written checks it replaces and
+    decides as each did on every call aten would accept: the operands of
+    an mm, addmm or gelu_backward share dtype and device, so it made no
+    difference that the mode-level check looked at the first operand
+    only, NativeWgradMode at both dtypes but one device, and the dgrad
+    route at dy.device == w.device without use_hip (the mode-level check
+    ahead of it had called it).  What one kernel asks beyond the gate
+    stays at its route: a 16-byte aligned W for _C.dgrad_tn, hid % 8 for
+    the GELU backward."""
+    dev = tensors[0].device
+    return all(
+        t.is_cuda and t.dtype == torch.bfloat16 and t.device == dev
+        for t in tensors
+    ) and use_hip(*tensors)
+
+
+def _wgemm_takes(at, b):
+    """mm(at, b) is a weight gradient that csrc/wgemm.hip takes."""
+    return (_is_wgrad_mm(at, b) and _hip_bf16(at, b)
+            and hasattr(ext(), "wgrad_gemm"))
+
+
+def _wgemm(at, b):
+    """dW [M, N] = at @ b by csrc/wgemm.hip, from the contiguous [K, M]
+    base of at and b [K, N]."""
+    (dw,) = ext().wgrad_gemm(at.t().contiguous(), b.contiguous(), False)
+    return dw
+
+
 class NativeWgradMode(TorchDispatchMode):
     """Reroute ONLY the dW GEMMs to csrc/wgemm.hip, below autograd.
 
@@ -349,33 +360,17 @@ class NativeWgradMode(TorchDispatchMode):
     def __init__(self, handler=None):
         super().__init__()
         self.hits = 0
-        self._handler = handler
-
-    def _route(self, at, b):
-        if self._handler is not None:
-            return self._handler(at.t(), b)
-        (dw,) = ext().wgrad_gemm(at.t().contiguous(), b.contiguous(), False)
-        return dw
+        if handler is None:
+            self._takes, self._kernel = _wgemm_takes, _wgemm
+        else:
+            self._takes = _is_wgrad_mm
+            self._kernel = lambda at, b: handler(at.t(), b)
 
     def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
-        if (
-            func is torch.ops.aten.mm.default
-            and _is_wgrad_mm(*args)
-            and (
-                self._handler is not None
-                or (
-                    args[0].is_cuda
-                    and args[0].dtype == torch.bfloat16
-                    and args[1].dtype == torch.bfloat16
-                    and use_hip(args[0])
-                    and hasattr(ext(), "wgrad_gemm")
-                )
-            )
-        ):
+        if func is torch.ops.aten.mm.default and self._takes(*args):
             self.hits += 1
-            return self._route(*args)
-        return func(*args, **kwargs)
+            return self._kernel(*args)
+        return func(*args, **(kwargs or {}))
 
 
 def _op_layout(t):
@@ -468,6 +463,45 @@ def _dgelu_dbias_on():
     )
 
 
+# --------------------------------------------------------------------------
+# The extension kernels behind the routes of TunedGemmMode, under the
+# names of its test seams.  A missing kernel is an error here, not a
+# fallback.
+# --------------------------------------------------------------------------
+
+
+def _lt_gemm(a, b, idx, bias):
+    """a @ b (+ bias) by hipBLASLt algorithm idx, -1 for its heuristic."""
+    return ext().lt_gemm(a, b, idx, bias)
+
+
+def _gelu_bwd_colsum(dy, x, want_t):
+    """(dx, bf16 column sums of dx, dx^T contiguous or None)."""
+    if want_t:
+        return ext().gelu_bwd_colsum_t(dy, x)
+    dx, colsum = ext().gelu_bwd_colsum(dy, x)
+    return dx, colsum, None
+
+
+def _transposed(t, want_colsum):
+    """(t^T contiguous, bf16 column sums of t or None)."""
+    if want_colsum:
+        tt, colsum = ext().transpose_colsum(t)
+        return tt, colsum
+    return ext().transpose2d(t), None
+
+
+def _dgrad_tn(dy, w, idx):
+    """dy @ w as the TN GEMM idx on w^T."""
+    return ext().dgrad_tn(dy, w, idx)
+
+
+_KERNELS = {"gemm": _lt_gemm, "dgelu": _gelu_bwd_colsum,
+            "transpose": _transposed, "dgrad": _dgrad_tn}
+
+# what an op method of TunedGemmMode returns for "not mine: run the stock op"
+_STOCK = object()
+
 
 class TunedGemmMode(TorchDispatchMode):
     """Reroute training GEMMs whose shape has an offline-searched
@@ -483,6 +517,13 @@ class TunedGemmMode(TorchDispatchMode):
     tuned N,N index at the shapes in its gate) and the fused MLP GELU
     epilogues when configured, so one mode covers the whole step (push
     around forward AND backward).
+
+    __torch_dispatch__ looks the op up in _OPS; the method found there
+    tries its routes in the order written and answers the op, or returns
+    _STOCK and the stock op runs.  Every kernel is called through _call
+    and every route asks _takes whether the tensors are its kernel's, so
+    the constructor's four handlers (fakes of the kernels in _KERNELS)
+    are consulted in those two places.
     """
 
     def __init__(self, table=None, native_wgrad=None, handler=None,
@@ -492,10 +533,24 @@ class TunedGemmMode(TorchDispatchMode):
         self.native_wgrad = (
             _NATIVE_WGRAD_DISPATCH if native_wgrad is None else native_wgrad
         )
-        # test seam: handler(a, b, idx, bias) replaces _C.lt_gemm (and
-        # lifts the CUDA/bf16 gate) so the routing logic runs on CPU
-        self._handler = handler
+        # test seams: a fake under a name of _KERNELS replaces that kernel
+        # and lifts the GPU gate for it, so that the routing logic runs
+        # on the CPU.  Signatures as in _KERNELS, except that the dgelu
+        # fake is dgelu_handler(dy, x) -> (dx, colsum), and that the gemm
+        # fake also stands in for _C.fwd_gemm_gelu when called with
+        # idx == "gelu" (-> (gelu output, pre-activation)).
+        fakes = {"gemm": handler, "dgelu": dgelu_handler,
+                 "transpose": tn_handler, "dgrad": dgrad_handler}
+        self._fakes = {k: f for k, f in fakes.items() if f is not None}
+
+        def on(switch, name=None):
+            # a route whose own kernel is not faked is off when the GEMM
+            # is: the real kernel could not take the fake GEMM's tensors
+            return switch and (name in self._fakes
+                               or "gemm" not in self._fakes)
+
         self.hits = 0
+        self._wgemm_on = on(self.native_wgrad)  # no seam of its own
         self.wgrad_hits = 0
         # fused-GELU state (see module comment above):
         self.fused_gelu = _gelu_fusion_on()
@@ -504,25 +559,15 @@ class TunedGemmMode(TorchDispatchMode):
         # and handed to another tensor while the key is live.
         self._pending_gelu = {}
         self.gelu_hits = 0
-        # fused dgelu + fc1 bias gradient (see module comment above).
-        # test seam: dgelu_handler(dy, x) -> (dx, colsum) replaces
-        # _C.gelu_bwd_colsum and lifts the CUDA/bf16 gate
-        self._dgelu_handler = dgelu_handler
-        self.fused_dgelu = _dgelu_dbias_on() and (
-            dgelu_handler is not None or self._handler is None
-        )
+        # fused dgelu + fc1 bias gradient (see module comment above)
+        self.fused_dgelu = on(_dgelu_dbias_on(), "dgelu")
         # (dx, colsum, dx^T or None): at most one entry
         self._dgelu_stash = None
         self.dgelu_hits = 0
         self.dbias_hits = 0
-        # TN weight gradients (see module comment above).
-        # test seam: tn_handler(t, want_colsum) -> (t^T contiguous,
-        # column sums or None) replaces _C.transpose2d /
-        # _C.transpose_colsum; the GEMM goes through ``handler``
-        self._tn_handler = tn_handler
-        self.tn_wgrad = _tn_wgrad_on() and (
-            tn_handler is not None or self._handler is None
-        )
+        # TN weight gradients (see module comment above); the GEMM goes
+        # through the gemm seam
+        self.tn_wgrad = on(_tn_wgrad_on(), "transpose")
         # (dy, colsum, dyT), at most one entry, holding dy so that its
         # address cannot be recycled.  After the GEMM: colsum waits for
         # the bias sum, dyT is None.  After a bias sum that came first:
@@ -534,13 +579,8 @@ class TunedGemmMode(TorchDispatchMode):
         self._tn_mm_first = False
         self.tn_hits = 0
         self.tn_dbias_hits = 0
-        # TN input gradients (see module comment above).
-        # test seam: dgrad_handler(dy, w, idx) -> dx replaces
-        # _C.dgrad_tn and lifts the CUDA/bf16 gate
-        self._dgrad_handler = dgrad_handler
-        self.tn_dgrad = _tn_dgrad_on() and (
-            dgrad_handler is not None or self._handler is None
-        )
+        # TN input gradients (see module comment above)
+        self.tn_dgrad = on(_tn_dgrad_on(), "dgrad")
         self.tn_dgrad_hits = 0
 
     def __exit__(self, exc_type, exc_val, exc_tb):
@@ -548,23 +588,138 @@ class TunedGemmMode(TorchDispatchMode):
         self._tn_stash = None
         return super().__exit__(exc_type, exc_val, exc_tb)
 
-    def _tuned_index(self, a, b):
-        if not self.table:
-            return None
+    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        op = self._OPS.get(func)
+        if op is not None:
+            out = op(self, args, kwargs)
+            if out is not _STOCK:
+                return out
+        return func(*args, **kwargs)
+
+    def _call(self, name, *args):
+        """The fake under this seam name if there is one, else the
+        extension's kernel."""
+        return self._fakes.get(name, _KERNELS[name])(*args)
+
+    def _takes(self, name, *tensors, kernel_ok=True):
+        """Whether the route that ends in this seam may take these
+        tensors: it is faked, or they pass the GPU gate and what the real
+        kernel asks beyond it (``kernel_ok``), which a fake does not."""
+        return name in self._fakes or (kernel_ok and _hip_bf16(*tensors))
+
+    def _tuned_index(self, key):
+        return self.table.get(key) if self.table and key is not None else None
+
+    # -- the ops, each with its routes in order of precedence ---------------
+
+    def _mm(self, args, kwargs):
+        a, b = args
+        # asked once for every route below: TN wgrad and the tuned index
+        # end in the GEMM seam, and wgemm and TN dgrad ask the same of
+        # the same two tensors
+        if not self._takes("gemm", a, b):
+            return _STOCK
+        if self.tn_wgrad and _is_tn_wgrad_mm(a, b):
+            return self._tn_wgrad(a, b)
+        if self._wgemm_on and _wgemm_takes(a, b):
+            self.wgrad_hits += 1
+            return _wgemm(a, b)
+        if self.tn_dgrad and self._is_tn_dgrad_mm(a, b):
+            return self._tn_dgrad(a, b)
+        idx = self._tuned_index(_dual_key(a, b))
+        if idx is None:
+            return _STOCK
+        self.hits += 1
+        return self._call("gemm", a, b, idx, None)
+
+    def _addmm(self, args, kwargs):
+        if not (
+            len(args) == 3
+            and kwargs.get("beta", 1) == 1
+            and kwargs.get("alpha", 1) == 1
+            and args[0].dim() == 1
+            and self._takes("gemm", *args)
+        ):
+            return _STOCK
+        bias, a, b = args
         key = _dual_key(a, b)
-        if key is None:
+        if (
+            self.fused_gelu
+            and self._is_fc1_fwd(key)
+            and ("gemm" in self._fakes or hasattr(ext(), "fwd_gemm_gelu"))
+        ):
+            return self._fused_fc1_fwd(a, b, bias)
+        idx = self._tuned_index(key)
+        if idx is None:
+            return _STOCK
+        self.hits += 1
+        return self._call("gemm", a, b, idx, bias)
+
+    def _gelu(self, args, kwargs):
+        if self.fused_gelu:
+            _, out = self._pending_gelu.pop(args[0].data_ptr(), (None, None))
+            if out is not None and out.shape == args[0].shape:
+                return out
+        return _STOCK
+
+    def _gelu_backward(self, args, kwargs):
+        if self.fused_dgelu and self._is_mlp_dgelu(args, kwargs):
+            return self._fused_dgelu(*args)
+        return _STOCK
+
+    def _take_parked(self, stash, t):
+        """The column sums parked in that stash if t is the tensor they
+        were taken from (which empties the stash), else None."""
+        st = getattr(self, stash)
+        if st is None or st[1] is None or not _same_buffer(t, st[0]):
             return None
-        return self.table.get(key)
+        setattr(self, stash, None)
+        return st[1]
 
-    def _gpu_ok(self, t):
-        if self._handler is not None:
-            return True
-        return t.is_cuda and t.dtype == torch.bfloat16 and use_hip(t)
+    def _sum(self, args, kwargs):
+        """A bias gradient whose column sums a kernel of ours has made
+        already, or, when the sum comes before its TN GEMM, makes here."""
+        if self._dgelu_stash is None and not self.tn_wgrad:
+            return _STOCK
+        rs = _row_sum_args(args, kwargs)
+        if rs is None:
+            return _STOCK
+        t, keepdim = rs
+        colsum = self._take_parked("_dgelu_stash", t)
+        if colsum is not None:
+            self.dbias_hits += 1
+        else:
+            colsum = self._take_parked("_tn_stash", t)
+            if (
+                colsum is None
+                and self.tn_wgrad
+                and not self._tn_mm_first
+                and t.dim() == 2
+                and self._takes("gemm", t)
+                and _tn_wgrad_out_ok(t.shape[1], t.shape[0])
+            ):
+                # the GEMM's other operand is not known yet, so this goes by
+                # dy's shape alone; a GEMM outside the gate leaves dy^T unused
+                dyT, colsum = self._call("transpose", t, True)
+                self._tn_stash = (t, None, dyT)
+            if colsum is None:
+                return _STOCK
+            self.tn_dbias_hits += 1
+        if keepdim:
+            return colsum.view([1] * (t.dim() - 1) + [t.shape[-1]])
+        return colsum
 
-    def _route(self, a, b, idx, bias=None):
-        if self._handler is not None:
-            return self._handler(a, b, idx, bias)
-        return ext().lt_gemm(a, b, idx, bias)
+    # what __torch_dispatch__ looks an op up in (a class-level table of
+    # plain functions: a per-mode table of bound methods would tie every
+    # mode into a reference cycle)
+    _OPS = {
+        torch.ops.aten.mm.default: _mm,
+        torch.ops.aten.addmm.default: _addmm,
+        torch.ops.aten.gelu.default: _gelu,
+        torch.ops.aten.gelu_backward.default: _gelu_backward,
+        torch.ops.aten.sum.dim_IntList: _sum,
+    }
 
     # -- fused-GELU helpers -------------------------------------------------
 
@@ -575,8 +730,8 @@ class TunedGemmMode(TorchDispatchMode):
             and key[2] == _GELU_CFG["hid"] and key[4] == _GELU_CFG["d"]
         ):
             return False
-        if self._handler is not None:
-            return True  # CPU test seam has no kernel shape limits
+        if "gemm" in self._fakes:
+            return True  # the fake has no kernel shape limits
         hid, tok = key[2], key[3]
         return (
             tok % 256 == 0 and hid % 256 == 0 and key[4] % 64 == 0
@@ -584,8 +739,8 @@ class TunedGemmMode(TorchDispatchMode):
         )
 
     def _fused_fc1_fwd(self, a, b, bias):
-        if self._handler is not None:  # CPU test seam
-            out, pre = self._handler(a, b, "gelu", bias)
+        if "gemm" in self._fakes:  # stands in for fwd_gemm_gelu
+            out, pre = self._fakes["gemm"](a, b, "gelu", bias)
         else:
             # b is the transposed view of fc1's weight [hid, d]: b.t()
             # IS the weight, row-major contiguous — fgemm reads it
@@ -612,69 +767,26 @@ class TunedGemmMode(TorchDispatchMode):
             and dy.is_contiguous() and x.is_contiguous()
         ):
             return False
-        if self._dgelu_handler is not None:
-            return True
-        return (
-            dy.is_cuda and dy.dtype == torch.bfloat16
-            and x.dtype == torch.bfloat16
-            and dy.shape[-1] % 8 == 0
-            and use_hip(dy)
-        )
+        # the kernel's rows are 16-byte vectors
+        return self._takes("dgelu", dy, x, kernel_ok=dy.shape[-1] % 8 == 0)
 
     def _fused_dgelu(self, dy, x):
         hid = dy.shape[-1]
         # fc1's weight gradient will want dx^T if it takes the TN route
         want_t = self.tn_dgelu_t and _tn_wgrad_shapes_ok(
             hid, _GELU_CFG["d"], dy.numel() // hid)
-        dxt = None
-        if self._dgelu_handler is not None:
-            dx, colsum = self._dgelu_handler(dy, x)
-            if want_t:
-                dxt = dx.reshape(-1, hid).t().contiguous()
-        elif want_t:
-            dx, colsum, dxt = ext().gelu_bwd_colsum_t(dy, x)
+        if "dgelu" in self._fakes:  # (dx, colsum) only: dx^T in torch
+            dx, colsum = self._fakes["dgelu"](dy, x)
+            dxt = dx.reshape(-1, hid).t().contiguous() if want_t else None
         else:
-            # a missing kernel is an error here, not a fallback
-            dx, colsum = ext().gelu_bwd_colsum(dy, x)
+            dx, colsum, dxt = _KERNELS["dgelu"](dy, x, want_t)
         self.dgelu_hits += 1
         # holding dx keeps its address from being recycled while the
         # entry lives; the next gelu_backward overwrites it
         self._dgelu_stash = (dx, colsum, dxt)
         return dx
 
-    def _stashed_dbias(self, args, kwargs):
-        """The parked column sums if this sum is dx.sum over every dim
-        but the last, else None."""
-        rs = _row_sum_args(args, kwargs)
-        if self._dgelu_stash is None or rs is None:
-            return None
-        dx, colsum = self._dgelu_stash[:2]
-        t, keepdim = rs
-        if not _same_buffer(t, dx):
-            return None
-        self._dgelu_stash = None
-        self.dbias_hits += 1
-        if keepdim:
-            return colsum.view([1] * (t.dim() - 1) + [t.shape[-1]])
-        return colsum
-
     # -- TN weight-gradient helpers ------------------------------------------
-
-    def _tn_transposed(self, t, want_colsum):
-        """(t^T contiguous, bf16 column sums of t or None)."""
-        if self._tn_handler is not None:
-            return self._tn_handler(t, want_colsum)
-        # a missing kernel is an error here, not a fallback
-        if want_colsum:
-            tt, colsum = ext().transpose_colsum(t)
-            return tt, colsum
-        return ext().transpose2d(t), None
-
-    def _is_tn_wgrad_mm(self, at, b):
-        dims = _wgrad_mm_dims(at, b)
-        if dims is None or not _tn_wgrad_shapes_ok(*dims):
-            return False
-        return self._handler is not None or b.dtype == torch.bfloat16
 
     def _tn_wgrad(self, at, x):
         """dW [out, in] contiguous = lt_gemm(dy^T, (x^T).t()).  The two
@@ -693,46 +805,17 @@ class TunedGemmMode(TorchDispatchMode):
                 # was told to write it
                 dx, colsum, dyT = self._dgelu_stash
                 if dyT is None:
-                    dyT, _ = self._tn_transposed(dy, False)
+                    dyT, _ = self._call("transpose", dy, False)
                 else:
                     self._dgelu_stash = (dx, colsum, None)
             else:
-                dyT, colsum = self._tn_transposed(dy, True)
+                dyT, colsum = self._call("transpose", dy, True)
                 self._tn_stash = (dy, colsum, None)
-        xT, _ = self._tn_transposed(x, False)
+        xT, _ = self._call("transpose", x, False)
         b = xT.t()
-        idx = self._tuned_index(dyT, b)
+        idx = self._tuned_index(_dual_key(dyT, b))
         self.tn_hits += 1
-        return self._route(dyT, b, -1 if idx is None else idx)
-
-    def _tn_dbias(self, args, kwargs):
-        """The column sums of dy for its bias gradient: the ones the
-        GEMM parked, or — when the sum comes before its GEMM — from the
-        pass done here, which parks dy^T for the GEMM.  Else None."""
-        rs = _row_sum_args(args, kwargs)
-        if rs is None:
-            return None
-        t, keepdim = rs
-        st = self._tn_stash
-        if st is not None and st[1] is not None and _same_buffer(t, st[0]):
-            colsum = st[1]
-            self._tn_stash = None
-        elif (
-            not self._tn_mm_first
-            and t.dim() == 2
-            and self._gpu_ok(t)
-            and _tn_wgrad_out_ok(t.shape[1], t.shape[0])
-        ):
-            # the GEMM's other operand is not known yet, so this goes by
-            # dy's shape alone; a GEMM outside the gate leaves dy^T unused
-            dyT, colsum = self._tn_transposed(t, True)
-            self._tn_stash = (t, None, dyT)
-        else:
-            return None
-        self.tn_dbias_hits += 1
-        if keepdim:
-            return colsum.view([1] * (t.dim() - 1) + [t.shape[-1]])
-        return colsum
+        return self._call("gemm", dyT, b, -1 if idx is None else idx, None)
 
     # -- TN input-gradient helpers -------------------------------------------
 
@@ -747,88 +830,16 @@ class TunedGemmMode(TorchDispatchMode):
             return False
         if not _tn_dgrad_shapes_ok(w.shape[0], w.shape[1], dy.shape[0]):
             return False
-        if self._dgrad_handler is not None:
-            return True
-        return (
-            w.is_cuda and w.dtype == torch.bfloat16
-            and dy.dtype == torch.bfloat16 and dy.device == w.device
-        )
+        return self._takes("dgrad", dy, w)
 
     def _tn_dgrad(self, dy, w):
         """dx = dy @ W as the TN GEMM on W^T, which _C.dgrad_tn writes
         and drops.  That GEMM is lt_gemm(dy, wT.t()), so its tuned index
         is the one under the dual key of a forward with these sizes."""
         out, inn = w.shape
-        idx = self.table.get(("T", "N", inn, dy.shape[0], out)) \
-            if self.table else None
-        idx = -1 if idx is None else idx
+        idx = self._tuned_index(("T", "N", inn, dy.shape[0], out))
         self.tn_dgrad_hits += 1
-        if self._dgrad_handler is not None:
-            return self._dgrad_handler(dy, w, idx)
-        # a missing kernel is an error here, not a fallback
-        return ext().dgrad_tn(dy, w, idx)
-
-    def __torch_dispatch__(self, func, types, args=(), kwargs=None):
-        kwargs = kwargs or {}
-        if func is torch.ops.aten.mm.default and self._gpu_ok(args[0]):
-            a, b = args
-            if self.tn_wgrad and self._is_tn_wgrad_mm(a, b):
-                return self._tn_wgrad(a, b)
-            if (
-                self.native_wgrad
-                and self._handler is None
-                and _is_wgrad_mm(a, b)
-                and hasattr(ext(), "wgrad_gemm")
-            ):
-                self.wgrad_hits += 1
-                (dw,) = ext().wgrad_gemm(a.t().contiguous(), b.contiguous(),
-                                         False)
-                return dw
-            if self.tn_dgrad and self._is_tn_dgrad_mm(a, b):
-                return self._tn_dgrad(a, b)
-            idx = self._tuned_index(a, b)
-            if idx is not None:
-                self.hits += 1
-                return self._route(a, b, idx)
-        elif (
-            func is torch.ops.aten.addmm.default
-            and len(args) == 3
-            and kwargs.get("beta", 1) == 1
-            and kwargs.get("alpha", 1) == 1
-            and self._gpu_ok(args[1])
-            and args[0].dim() == 1
-        ):
-            bias, a, b = args
-            key = _dual_key(a, b)
-            if (
-                self.fused_gelu
-                and self._is_fc1_fwd(key)
-                and (self._handler is not None
-                     or hasattr(ext(), "fwd_gemm_gelu"))
-            ):
-                return self._fused_fc1_fwd(a, b, bias)
-            idx = self.table.get(key) if (self.table and key) else None
-            if idx is not None:
-                self.hits += 1
-                return self._route(a, b, idx, bias)
-        elif self.fused_gelu and func is torch.ops.aten.gelu.default:
-            _, out = self._pending_gelu.pop(args[0].data_ptr(), (None, None))
-            if out is not None and out.shape == args[0].shape:
-                return out
-        elif self.fused_dgelu and func is torch.ops.aten.gelu_backward.default:
-            if self._is_mlp_dgelu(args, kwargs):
-                return self._fused_dgelu(*args)
-        elif func is torch.ops.aten.sum.dim_IntList and (
-            self._dgelu_stash is not None or self.tn_wgrad
-        ):
-            out = None
-            if self._dgelu_stash is not None:
-                out = self._stashed_dbias(args, kwargs)
-            if out is None and self.tn_wgrad:
-                out = self._tn_dbias(args, kwargs)
-            if out is not None:
-                return out
-        return func(*args, **kwargs)
+        return self._call("dgrad", dy, w, -1 if idx is None else idx)
 
 
 def gemm_dispatch_context():
@@ -845,12 +856,6 @@ def gemm_dispatch_context():
     if _NATIVE_WGRAD_DISPATCH:
         return NativeWgradMode()  # backward-compatible, wgrad only
     return contextlib.nullcontext()
-
-
-def wgrad_backward_context():
-    """Backward-compatible alias of gemm_dispatch_context (historical
-    name from when only the dW GEMMs were rerouted)."""
-    return gemm_dispatch_context()
 
 
 class NativeLinear(nn.Linear):

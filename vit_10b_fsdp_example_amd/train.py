@@ -127,8 +127,10 @@ def train(cfg):
             if max_steps and step >= max_steps:
                 break
             # 1-2. forward + backward under the GEMM dispatch router
-            # (no-op unless a tuned hipBLASLt table is present or
-            # VITFSDP_NATIVE_WGRAD=2 routes dW to csrc/wgemm.hip)
+            # (TunedGemmMode when a tuned hipBLASLt table is present or
+            # the MLP dims are configured for a fused GELU pass, which a
+            # ViT's are by default; else NativeWgradMode under
+            # VITFSDP_NATIVE_WGRAD=2, else a no-op: ops/linear.py)
             with gemm_dispatch_context():
                 output = model(data)
                 loss = loss_fn(output, target)
