@@ -59,6 +59,12 @@ torch::Tensor fmha_rowdot(torch::Tensor dout, torch::Tensor o);
 std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x);
 std::vector<torch::Tensor> gelu_bwd_colsum_t(torch::Tensor dy,
                                              torch::Tensor x);
+std::vector<torch::Tensor> gelu_dropout_bwd_colsum(torch::Tensor dy,
+                                                   torch::Tensor x, double p,
+                                                   long seed);
+std::vector<torch::Tensor> gelu_dropout_bwd_colsum_t(torch::Tensor dy,
+                                                     torch::Tensor x, double p,
+                                                     long seed);
 torch::Tensor transpose2d(torch::Tensor x);
 std::vector<torch::Tensor> transpose_colsum(torch::Tensor x);
 torch::Tensor dropout_fwd(torch::Tensor x, double p, long seed);
@@ -165,6 +171,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_dropout_bwd", &gelu_dropout_bwd,
         "backward of gelu_dropout_fwd from dy and the pre-activation x; "
         "regenerates the mask from the seed",
+        py::arg("dy"), py::arg("x"), py::arg("p"), py::arg("seed"));
+  m.def("gelu_dropout_bwd_colsum", &gelu_dropout_bwd_colsum,
+        "(dx, colsum): gelu_dropout_bwd and the bf16 column sums of dx "
+        "over all rows (fc1 bias gradient) in one pass; dx is "
+        "bit-identical to gelu_dropout_bwd's",
+        py::arg("dy"), py::arg("x"), py::arg("p"), py::arg("seed"));
+  m.def("gelu_dropout_bwd_colsum_t", &gelu_dropout_bwd_colsum_t,
+        "(dx, colsum, dx^T): gelu_dropout_bwd_colsum with dx^T [hid, rows] "
+        "as a third output; dx and colsum are bit-identical to "
+        "gelu_dropout_bwd_colsum's",
         py::arg("dy"), py::arg("x"), py::arg("p"), py::arg("seed"));
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("mfma32_probe", &mfma32_probe, "32x32x16 bf16 MFMA layout probe");

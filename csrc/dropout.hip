@@ -13,6 +13,11 @@
 //   gelu_dropout_fwd   y = keep ? gelu(x) * rscale : 0
 //   gelu_dropout_bwd   dx = keep ? gelu'(x) * dy * rscale : 0
 //
+// gelu_dropout_bwd with the column sums of dx (fc1's bias gradient) and
+// dx^T in the same pass is gelu_dropout_bwd_colsum(_t) in gelu.hip, next
+// to the p = 0 kernels it shares everything but the element formula
+// with; its dx is this file's bit for bit.
+//
 // Dropped elements are SELECTED to +0 (not multiplied by 0), so a
 // non-finite value under a dropped position does not leak; at kept
 // positions it propagates.  All arithmetic is fp32 with one bf16

@@ -11,6 +11,14 @@
 // Memory-bound: two bf16 streams in, one out, 16-byte vectors.  Each
 // thread owns ONE 8-wide vector column and walks the rows of its chunk,
 // so its 8 column sums stay in registers; grid = (hid/8/256, chunks).
+//
+// With hidden dropout behind the GELU (--mlp_dropout > 0) the same two
+// kernels run as their DROP instantiations: dx is the backward of
+// dropout(gelu(x)), bit for bit what gelu_dropout_bwd (dropout.hip)
+// writes, the mask regenerated from (seed, flattened row, column), and
+// the sums run over that dx, dropped zeros included.  Only the element
+// formula differs (dgelu_elem below); chunks, tiles and the order of
+// every sum are those of the plain instantiations.
 
 #ifndef VITFSDP_KERNELS_ONLY
 #include <ATen/cuda/CUDAContext.h>
@@ -25,12 +33,42 @@ namespace {
 
 constexpr int kBlock = 256;
 
+// The mask of the DROP instantiations: element (row, col) is kept iff
+// dropout_hash(seed, row, col) >= thresh, and a kept dy is scaled by
+// rscale (thresh and rscale as launch<> in dropout.hip computes them).
+struct DropArgs {
+  unsigned thresh;
+  float rscale;
+  unsigned seed;
+};
+
+// One element of dx.  DROP: the expression of
+// hidden_dropout_kernel<kGeluDropBwd>, a dropped element SELECTED to +0.
+template <bool DROP>
+__device__ __forceinline__ unsigned short dgelu_elem(unsigned short dy,
+                                                     unsigned short x,
+                                                     const DropArgs& d,
+                                                     unsigned row,
+                                                     unsigned col) {
+  if constexpr (DROP) {
+    const bool keep = dropout_hash(d.seed, row, col) >= d.thresh;
+    return keep ? f32_to_bf16(
+                      gelu_bwd_one(bf16_to_f32(dy) * d.rscale, bf16_to_f32(x)))
+                : (unsigned short)0;
+  } else {
+    return f32_to_bf16(gelu_bwd_one(bf16_to_f32(dy), bf16_to_f32(x)));
+  }
+}
+
+template <bool DROP>
 __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_kernel(
     const ushort8_t* __restrict__ dy, const ushort8_t* __restrict__ x,
     ushort8_t* __restrict__ dx, float* __restrict__ part, int nvec,
-    long n_rows, int rows_per_chunk) {
+    long n_rows, int rows_per_chunk, DropArgs drop) {
   const int vc = blockIdx.x * kBlock + threadIdx.x;
   if (vc >= nvec) return;
+  // the column half of the hash does not change along the row walk
+  const unsigned c0 = (unsigned)vc * 8u;
   const long row_begin = (long)blockIdx.y * rows_per_chunk;
   const long row_end = min(row_begin + rows_per_chunk, n_rows);
   float acc[8];
@@ -43,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_kernel(
     ushort8_t out;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      out[j] = f32_to_bf16(gelu_bwd_one(bf16_to_f32(dv[j]), bf16_to_f32(xv[j])));
+      out[j] = dgelu_elem<DROP>(dv[j], xv[j], drop, (unsigned)r, c0 + j);
       // the sum is over the ROUNDED values: it equals dx.sum(0)
       acc[j] += bf16_to_f32(out[j]);
     }
@@ -76,10 +114,12 @@ constexpr int kTRows = 64;
 constexpr int kTCols = 256;
 constexpr int kTSlots = kTCols / 8;
 
+template <bool DROP>
 __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
     const unsigned short* __restrict__ dy, const unsigned short* __restrict__ x,
     unsigned short* __restrict__ dx, unsigned short* __restrict__ dxt,
-    float* __restrict__ part, long hid, long n_rows, int rows_per_chunk) {
+    float* __restrict__ part, long hid, long n_rows, int rows_per_chunk,
+    DropArgs drop) {
   __shared__ ushort8_t tile[kTRows * kTSlots];
   const unsigned short* tile_s = reinterpret_cast<const unsigned short*>(tile);
   const int t = threadIdx.x;
@@ -89,6 +129,7 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
   const bool vec_store = (n_rows & 7) == 0;  // dx^T rows 16-byte aligned
   const int a_slot = t & 31, a_row = t >> 5;  // (A): rows a_row + 8k
   const bool a_col_ok = c0 + a_slot * 8 < hid;
+  const unsigned a_c0 = (unsigned)(c0 + a_slot * 8);  // (A): first column
   const int c_hi = t >> 3, c_lo = t & 7;  // (C): column c_hi + 32k, rows 8 c_lo..
   float acc = 0.f;
 
@@ -105,8 +146,8 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
         ushort8_t out;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          out[j] = f32_to_bf16(
-              gelu_bwd_one(bf16_to_f32(dv[j]), bf16_to_f32(xv[j])));
+          out[j] =
+              dgelu_elem<DROP>(dv[j], xv[j], drop, (unsigned)gr, a_c0 + j);
         *reinterpret_cast<ushort8_t*>(dx + i) = out;
         tile[r * kTSlots + (a_slot ^ ((r >> 3) & 7))] = out;
       }
@@ -147,6 +188,20 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
   if (c0 + t < hid) part[(long)blockIdx.y * hid + c0 + t] = acc;
 }
 
+#ifdef VITFSDP_KERNELS_ONLY
+// explicit instantiations so -Rpass-analysis reports every kernel
+#define VITFSDP_INSTANTIATE_DGELU(DROP_)                                     \
+  template __global__ void gelu_bwd_colsum_kernel<DROP_>(                    \
+      const ushort8_t*, const ushort8_t*, ushort8_t*, float*, int, long,     \
+      int, DropArgs);                                                        \
+  template __global__ void gelu_bwd_colsum_t_kernel<DROP_>(                  \
+      const unsigned short*, const unsigned short*, unsigned short*,         \
+      unsigned short*, float*, long, long, int, DropArgs);
+VITFSDP_INSTANTIATE_DGELU(false)
+VITFSDP_INSTANTIATE_DGELU(true)
+#undef VITFSDP_INSTANTIATE_DGELU
+#endif
+
 }  // namespace
 
 #ifndef VITFSDP_KERNELS_ONLY
@@ -154,37 +209,37 @@ namespace {
 
 // dy, x: bf16 [rows, hid] contiguous (any leading dims), hid % 8 == 0.
 // Returns (dx like dy, colsum bf16 [hid]) and, with_t, dx^T [hid, rows].
-std::vector<torch::Tensor> gelu_bwd_colsum_run(torch::Tensor dy,
-                                               torch::Tensor x, bool with_t);
-
-}  // namespace
-
-std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x) {
-  return gelu_bwd_colsum_run(dy, x, false);
-}
-
-std::vector<torch::Tensor> gelu_bwd_colsum_t(torch::Tensor dy,
-                                             torch::Tensor x) {
-  return gelu_bwd_colsum_run(dy, x, true);
-}
-
-namespace {
-
-std::vector<torch::Tensor> gelu_bwd_colsum_run(torch::Tensor dy,
-                                               torch::Tensor x, bool with_t) {
+// DROP: 0 < p < 1 and the seed of the forward's mask; unused otherwise.
+template <bool DROP>
+std::vector<torch::Tensor> gelu_bwd_colsum_run(const char* op,
+                                               torch::Tensor dy,
+                                               torch::Tensor x, bool with_t,
+                                               double p, long seed) {
   TORCH_CHECK(dy.is_cuda() && x.is_cuda() && dy.is_contiguous() &&
                   x.is_contiguous(),
-              "gelu_bwd_colsum: contiguous GPU tensors");
+              op, ": contiguous GPU tensors");
   TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 &&
                   x.scalar_type() == torch::kBFloat16,
-              "gelu_bwd_colsum: bf16 only");
-  TORCH_CHECK(dy.dim() >= 1 && dy.sizes() == x.sizes(),
-              "gelu_bwd_colsum: dy and x must have one shape");
+              op, ": bf16 only");
+  TORCH_CHECK(dy.dim() >= 1 && dy.sizes() == x.sizes() &&
+                  dy.device() == x.device(),
+              op, ": dy and x must have one shape");
   const long hid = dy.size(-1);
-  TORCH_CHECK(hid > 0 && hid % 8 == 0,
-              "gelu_bwd_colsum: last dim must be a multiple of 8, got ", hid);
-  TORCH_CHECK(hid < (1L << 31), "gelu_bwd_colsum: last dim too large");
+  TORCH_CHECK(hid > 0 && hid % 8 == 0, op,
+              ": last dim must be a multiple of 8, got ", hid);
+  TORCH_CHECK(hid < (1L << 31), op, ": last dim too large");
   const long n = dy.numel() / hid;
+  DropArgs drop = {0u, 1.f, 0u};
+  if (DROP) {
+    TORCH_CHECK(p > 0.0 && p < 1.0, op, ": p must be in (0, 1), got ", p);
+    // the hash takes the flattened row as 32 bits
+    TORCH_CHECK(n < (1L << 32), op, ": rows must be below 2^32");
+    // in double, exactly as launch<> in dropout.hip
+    const uint64_t t64 = (uint64_t)(p * 4294967296.0);
+    drop.thresh = t64 > 4294967295ull ? 4294967295u : (unsigned)t64;
+    drop.rscale = (float)(1.0 / (1.0 - p));
+    drop.seed = (unsigned)seed;
+  }
   auto dx = torch::empty_like(dy);
   auto colsum = torch::empty({hid}, dy.options());
   torch::Tensor dxt;
@@ -201,26 +256,26 @@ std::vector<torch::Tensor> gelu_bwd_colsum_run(torch::Tensor dy,
   long n_chunks = std::max(1, 2048 / grid_x);
   long rows_per_chunk = std::max<long>((n + n_chunks - 1) / n_chunks, 16);
   n_chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-  TORCH_CHECK(n_chunks <= 65535, "gelu_bwd_colsum: too many rows");
+  TORCH_CHECK(n_chunks <= 65535, op, ": too many rows");
   auto part = torch::empty({n_chunks, hid},
                            dy.options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentCUDAStream();
   if (with_t) {
     // the same chunks, so the same partials; only the block shape differs
     hipLaunchKernelGGL(
-        gelu_bwd_colsum_t_kernel,
+        gelu_bwd_colsum_t_kernel<DROP>,
         dim3((unsigned)((hid + kTCols - 1) / kTCols), (unsigned)n_chunks),
         dim3(kBlock), 0, stream, (const unsigned short*)dy.data_ptr(),
         (const unsigned short*)x.data_ptr(), (unsigned short*)dx.data_ptr(),
         (unsigned short*)dxt.data_ptr(), part.data_ptr<float>(), hid, n,
-        (int)rows_per_chunk);
+        (int)rows_per_chunk, drop);
   } else {
-    hipLaunchKernelGGL(gelu_bwd_colsum_kernel,
+    hipLaunchKernelGGL(gelu_bwd_colsum_kernel<DROP>,
                        dim3(grid_x, (unsigned)n_chunks), dim3(kBlock), 0,
                        stream, (const ushort8_t*)dy.data_ptr(),
                        (const ushort8_t*)x.data_ptr(),
                        (ushort8_t*)dx.data_ptr(), part.data_ptr<float>(), nvec,
-                       n, (int)rows_per_chunk);
+                       n, (int)rows_per_chunk, drop);
   }
   HIP_CHECK_LAST();
   hipLaunchKernelGGL(colsum_final_kernel, colsum_final_grid(hid),
@@ -233,4 +288,30 @@ std::vector<torch::Tensor> gelu_bwd_colsum_run(torch::Tensor dy,
 }
 
 }  // namespace
+
+std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x) {
+  return gelu_bwd_colsum_run<false>("gelu_bwd_colsum", dy, x, false, 0.0, 0);
+}
+
+std::vector<torch::Tensor> gelu_bwd_colsum_t(torch::Tensor dy,
+                                             torch::Tensor x) {
+  return gelu_bwd_colsum_run<false>("gelu_bwd_colsum", dy, x, true, 0.0, 0);
+}
+
+// (dx, colsum) with dx bit-identical to gelu_dropout_bwd(dy, x, p, seed)
+std::vector<torch::Tensor> gelu_dropout_bwd_colsum(torch::Tensor dy,
+                                                   torch::Tensor x, double p,
+                                                   long seed) {
+  return gelu_bwd_colsum_run<true>("gelu_dropout_bwd_colsum", dy, x, false, p,
+                                   seed);
+}
+
+// (dx, colsum, dx^T); dx and colsum bit-identical to the plain variant's
+std::vector<torch::Tensor> gelu_dropout_bwd_colsum_t(torch::Tensor dy,
+                                                     torch::Tensor x, double p,
+                                                     long seed) {
+  return gelu_bwd_colsum_run<true>("gelu_dropout_bwd_colsum", dy, x, true, p,
+                                   seed);
+}
 #endif  // VITFSDP_KERNELS_ONLY
+

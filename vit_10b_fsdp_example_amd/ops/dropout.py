@@ -17,6 +17,16 @@ it off.  In every other case the functions run exactly the stock
 composition (F.dropout / F.gelu), so CPU results and RNG consumption are
 those of nn.Dropout, and with p == 0 aten.gelu / aten.gelu_backward are
 still issued for the TunedGemmMode intercepts in ops/linear.py.
+
+The backward of gelu_dropout is issued as the registered op
+vitfsdp::gelu_dropout_bwd (schema in ops/linear.py, implementations
+here: _C.gelu_dropout_bwd on the GPU, plain torch elsewhere).  With no
+dispatch mode active that is the kernel call it replaced; under
+TunedGemmMode the op is answered by _C.gelu_dropout_bwd_colsum, which
+writes the same dx together with fc1's bias gradient, as the p == 0
+path does through aten.gelu_backward (the variant that also writes dx^T
+for fc1's TN weight gradient is not routed: _DGELU_DROP_T in
+ops/linear.py).
 """
 
 import os
@@ -27,6 +37,7 @@ import torch.nn.functional as F
 
 from ._extension import ext, use_hip
 from .attention import _draw_seed, dropout_mask_reference
+from . import linear as _linear
 from .linear import _gelu_fusion_on
 
 
@@ -89,7 +100,10 @@ class _GeluDropoutFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        dx = ext().gelu_dropout_bwd(dy.contiguous(), x, ctx.p, ctx.seed)
+        # as a registered op, so that TunedGemmMode can answer it with
+        # the kernel that also makes fc1's bias gradient and dx^T
+        dx = torch.ops.vitfsdp.gelu_dropout_bwd(
+            dy.contiguous(), x, ctx.p, ctx.seed)
         return dx, None, None
 
 
@@ -158,6 +172,25 @@ def _mask_and_scale(x, p, seed):
     cols = x.shape[-1]
     mask = hidden_dropout_mask(seed, x.numel() // cols, cols, p)
     return mask.reshape(x.shape).to(x.device), 1.0 / (1.0 - p)
+
+
+def _gelu_dropout_bwd_gpu(dy, x, p, seed):
+    return ext().gelu_dropout_bwd(dy, x, p, seed)
+
+
+def _gelu_dropout_bwd_torch(dy, x, p, seed):
+    """vitfsdp::gelu_dropout_bwd away from the GPU, in plain torch (the
+    native forward never runs there; this serves CPU tests of the
+    routing)."""
+    mask, rscale = _mask_and_scale(x, p, seed)
+    dx = torch.ops.aten.gelu_backward(dy * rscale, x, approximate="none")
+    return torch.where(mask, dx, torch.zeros_like(dx))
+
+
+# the schema is in ops/linear.py, next to the dispatch mode that routes it
+_linear._LIB.impl("gelu_dropout_bwd", _gelu_dropout_bwd_gpu, "CUDA")
+_linear._LIB.impl("gelu_dropout_bwd", _gelu_dropout_bwd_torch,
+                  "CompositeExplicitAutograd")
 
 
 def hidden_dropout_reference(x, p, seed):

@@ -165,7 +165,8 @@ def _is_wgrad_mm(at, b):
 #     mm(dy, W) ; mm(dy.t(), x) -> [out, in] ; sum.dim_IntList(dy, [0], True)
 # and the route answers the second and third; either may come first.
 # fc1's dy^T is a third output of the GELU backward
-# (_C.gelu_bwd_colsum_t, VITFSDP_TN_DGELU_T).
+# (_C.gelu_bwd_colsum_t, VITFSDP_TN_DGELU_T; behind hidden dropout see
+# _DGELU_DROP_T below).
 #
 # Gate: the shapes that won both isolated and in the step, fc1 and fc2
 # (_TN_WGRAD_SHAPES); proj loses and qkv leads the wgemm.hip path by less
@@ -464,6 +465,35 @@ def _dgelu_dbias_on():
 
 
 # --------------------------------------------------------------------------
+# The same with hidden dropout behind the GELU (--mlp_dropout > 0).  There
+# the backward of dropout(gelu(x)) is one kernel of ours
+# (_C.gelu_dropout_bwd, issued by ops/dropout.py), not an aten op, and a
+# dispatch mode sees aten and registered ops only.  So that backward is a
+# registered op, defined here because the _OPS table of TunedGemmMode
+# needs the op object; ops/dropout.py registers its implementations and
+# issues it.  The route answers it with _C.gelu_dropout_bwd_colsum(_t),
+# whose dx is bit-identical, and parks (dx, colsum, dx^T) in the stash of
+# the p = 0 route, so that the bias sum and the TN GEMM find it as they
+# find gelu_bwd_colsum's.  The same switch turns both off.
+# --------------------------------------------------------------------------
+
+# Whether the route uses _C.gelu_dropout_bwd_colsum_t where fc1's weight
+# gradient takes the TN route.  Off: at (32768, 20480), p = 0.1 that
+# kernel took 1.37-1.43 ms against 1.42-1.49 ms for gelu_dropout_bwd +
+# transpose_colsum, a lead smaller than the spread of either between
+# series (profiles/PROFILES.md "Hidden dropout"), and the plain kernel
+# followed by transpose2d would read dx once more than those two.  So at
+# such a shape the route declines and the two-pass sequence runs;
+# everywhere else (and with VITFSDP_TN_DGELU_T=0) it is the plain kernel,
+# which won by 13 %.
+_DGELU_DROP_T = False
+
+_LIB = torch.library.Library("vitfsdp", "DEF")
+_LIB.define(
+    "gelu_dropout_bwd(Tensor dy, Tensor x, float p, int seed) -> Tensor")
+
+
+# --------------------------------------------------------------------------
 # The extension kernels behind the routes of TunedGemmMode, under the
 # names of its test seams.  A missing kernel is an error here, not a
 # fallback.
@@ -483,6 +513,15 @@ def _gelu_bwd_colsum(dy, x, want_t):
     return dx, colsum, None
 
 
+def _gelu_dropout_bwd_colsum(dy, x, p, seed, want_t):
+    """_gelu_bwd_colsum for the backward of dropout(gelu(x)) under the
+    hash mask of (seed, p)."""
+    if want_t:
+        return ext().gelu_dropout_bwd_colsum_t(dy, x, p, seed)
+    dx, colsum = ext().gelu_dropout_bwd_colsum(dy, x, p, seed)
+    return dx, colsum, None
+
+
 def _transposed(t, want_colsum):
     """(t^T contiguous, bf16 column sums of t or None)."""
     if want_colsum:
@@ -497,6 +536,7 @@ def _dgrad_tn(dy, w, idx):
 
 
 _KERNELS = {"gemm": _lt_gemm, "dgelu": _gelu_bwd_colsum,
+            "dgelu_drop": _gelu_dropout_bwd_colsum,
             "transpose": _transposed, "dgrad": _dgrad_tn}
 
 # what an op method of TunedGemmMode returns for "not mine: run the stock op"
@@ -522,12 +562,13 @@ class TunedGemmMode(TorchDispatchMode):
     tries its routes in the order written and answers the op, or returns
     _STOCK and the stock op runs.  Every kernel is called through _call
     and every route asks _takes whether the tensors are its kernel's, so
-    the constructor's four handlers (fakes of the kernels in _KERNELS)
-    are consulted in those two places.
+    the constructor's handlers (fakes of the kernels in _KERNELS) are
+    consulted in those two places.
     """
 
     def __init__(self, table=None, native_wgrad=None, handler=None,
-                 dgelu_handler=None, tn_handler=None, dgrad_handler=None):
+                 dgelu_handler=None, tn_handler=None, dgrad_handler=None,
+                 *, dgelu_drop_handler=None):
         super().__init__()
         self.table = lt_algo_table() if table is None else table
         self.native_wgrad = (
@@ -536,10 +577,12 @@ class TunedGemmMode(TorchDispatchMode):
         # test seams: a fake under a name of _KERNELS replaces that kernel
         # and lifts the GPU gate for it, so that the routing logic runs
         # on the CPU.  Signatures as in _KERNELS, except that the dgelu
-        # fake is dgelu_handler(dy, x) -> (dx, colsum), and that the gemm
-        # fake also stands in for _C.fwd_gemm_gelu when called with
-        # idx == "gelu" (-> (gelu output, pre-activation)).
+        # fake is dgelu_handler(dy, x) -> (dx, colsum) and the dgelu_drop
+        # fake dgelu_drop_handler(dy, x, p, seed) -> (dx, colsum), and
+        # that the gemm fake also stands in for _C.fwd_gemm_gelu when
+        # called with idx == "gelu" (-> (gelu output, pre-activation)).
         fakes = {"gemm": handler, "dgelu": dgelu_handler,
+                 "dgelu_drop": dgelu_drop_handler,
                  "transpose": tn_handler, "dgrad": dgrad_handler}
         self._fakes = {k: f for k, f in fakes.items() if f is not None}
 
@@ -561,9 +604,12 @@ class TunedGemmMode(TorchDispatchMode):
         self.gelu_hits = 0
         # fused dgelu + fc1 bias gradient (see module comment above)
         self.fused_dgelu = on(_dgelu_dbias_on(), "dgelu")
-        # (dx, colsum, dx^T or None): at most one entry
+        # the same behind hidden dropout (vitfsdp::gelu_dropout_bwd)
+        self.fused_dgelu_drop = on(_dgelu_dbias_on(), "dgelu_drop")
+        # (dx, colsum, dx^T or None) of either route: at most one entry
         self._dgelu_stash = None
         self.dgelu_hits = 0
+        self.dgelu_drop_hits = 0
         self.dbias_hits = 0
         # TN weight gradients (see module comment above); the GEMM goes
         # through the gemm seam
@@ -668,6 +714,15 @@ class TunedGemmMode(TorchDispatchMode):
             return self._fused_dgelu(*args)
         return _STOCK
 
+    def _gelu_dropout_bwd(self, args, kwargs):
+        if (self.fused_dgelu_drop and len(args) == 4 and not kwargs
+                and self._is_mlp_dgelu_pair("dgelu_drop", *args[:2])
+                # see _DGELU_DROP_T: dx^T is wanted, and that kernel is
+                # not routed
+                and (_DGELU_DROP_T or not self._wants_dgelu_t(args[0]))):
+            return self._fused_dgelu_drop(*args)
+        return _STOCK  # the implementation ops/dropout.py registered
+
     def _take_parked(self, stash, t):
         """The column sums parked in that stash if t is the tensor they
         were taken from (which empties the stash), else None."""
@@ -718,6 +773,7 @@ class TunedGemmMode(TorchDispatchMode):
         torch.ops.aten.addmm.default: _addmm,
         torch.ops.aten.gelu.default: _gelu,
         torch.ops.aten.gelu_backward.default: _gelu_backward,
+        torch.ops.vitfsdp.gelu_dropout_bwd.default: _gelu_dropout_bwd,
         torch.ops.aten.sum.dim_IntList: _sum,
     }
 
@@ -759,7 +815,11 @@ class TunedGemmMode(TorchDispatchMode):
     def _is_mlp_dgelu(self, args, kwargs):
         if len(args) != 2 or kwargs.get("approximate", "none") != "none":
             return False
-        dy, x = args
+        return self._is_mlp_dgelu_pair("dgelu", *args)
+
+    def _is_mlp_dgelu_pair(self, name, dy, x):
+        """dy and x are those of the MLP's GELU backward, and the kernel
+        behind this seam name takes them."""
         if not (
             dy.dim() >= 2
             and dy.shape[-1] == _GELU_CFG["hid"]
@@ -768,22 +828,38 @@ class TunedGemmMode(TorchDispatchMode):
         ):
             return False
         # the kernel's rows are 16-byte vectors
-        return self._takes("dgelu", dy, x, kernel_ok=dy.shape[-1] % 8 == 0)
+        return self._takes(name, dy, x, kernel_ok=dy.shape[-1] % 8 == 0)
 
-    def _fused_dgelu(self, dy, x):
+    def _wants_dgelu_t(self, dy):
+        """fc1's weight gradient will take the TN route and expects dx^T
+        from the GELU backward."""
         hid = dy.shape[-1]
-        # fc1's weight gradient will want dx^T if it takes the TN route
-        want_t = self.tn_dgelu_t and _tn_wgrad_shapes_ok(
+        return self.tn_dgelu_t and _tn_wgrad_shapes_ok(
             hid, _GELU_CFG["d"], dy.numel() // hid)
-        if "dgelu" in self._fakes:  # (dx, colsum) only: dx^T in torch
-            dx, colsum = self._fakes["dgelu"](dy, x)
+
+    def _dgelu_kernel(self, name, dy, x, *mask):
+        """The kernel or the fake under this seam name, with dx^T if fc1's
+        weight gradient will take the TN route; parks what it returns."""
+        hid = dy.shape[-1]
+        want_t = self._wants_dgelu_t(dy)
+        if name in self._fakes:  # (dx, colsum) only: dx^T in torch
+            dx, colsum = self._fakes[name](dy, x, *mask)
             dxt = dx.reshape(-1, hid).t().contiguous() if want_t else None
         else:
-            dx, colsum, dxt = _KERNELS["dgelu"](dy, x, want_t)
-        self.dgelu_hits += 1
+            dx, colsum, dxt = _KERNELS[name](dy, x, *mask, want_t)
         # holding dx keeps its address from being recycled while the
-        # entry lives; the next gelu_backward overwrites it
+        # entry lives; the next GELU backward overwrites it
         self._dgelu_stash = (dx, colsum, dxt)
+        return dx
+
+    def _fused_dgelu(self, dy, x):
+        dx = self._dgelu_kernel("dgelu", dy, x)
+        self.dgelu_hits += 1
+        return dx
+
+    def _fused_dgelu_drop(self, dy, x, p, seed):
+        dx = self._dgelu_kernel("dgelu_drop", dy, x, float(p), int(seed))
+        self.dgelu_drop_hits += 1
         return dx
 
     # -- TN weight-gradient helpers ------------------------------------------
