@@ -73,6 +73,11 @@ torch::Tensor dropout_add_fwd(torch::Tensor x, torch::Tensor res, double p,
 torch::Tensor gelu_dropout_fwd(torch::Tensor x, double p, long seed);
 torch::Tensor gelu_dropout_bwd(torch::Tensor dy, torch::Tensor x, double p,
                                long seed);
+torch::Tensor drop_path_fwd(torch::Tensor x, long n_samples, double p_path,
+                            long seed_path, double p_elem, long seed_elem);
+torch::Tensor drop_path_add_fwd(torch::Tensor x, torch::Tensor res,
+                                long n_samples, double p_path, long seed_path,
+                                double p_elem, long seed_elem);
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma32_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor tr16_probe(long mode);
@@ -182,6 +187,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "as a third output; dx and colsum are bit-identical to "
         "gelu_dropout_bwd_colsum's",
         py::arg("dy"), py::arg("x"), py::arg("p"), py::arg("seed"));
+  m.def("drop_path_fwd", &drop_path_fwd,
+        "stochastic depth with the branch's element dropout folded in: "
+        "sample b = row / (rows / n_samples) is kept iff "
+        "dropout_hash(seed_path, b, 0) passes p_path; a dropped sample's "
+        "rows are written as zeros without being read; the same call on "
+        "dy is its backward",
+        py::arg("x"), py::arg("n_samples"), py::arg("p_path"),
+        py::arg("seed_path"), py::arg("p_elem"), py::arg("seed_elem"));
+  m.def("drop_path_add_fwd", &drop_path_add_fwd,
+        "x + drop_path(res) in one pass, rounded once; a dropped sample's "
+        "rows of res are not read and x passes through bit for bit",
+        py::arg("x"), py::arg("res"), py::arg("n_samples"),
+        py::arg("p_path"), py::arg("seed_path"), py::arg("p_elem"),
+        py::arg("seed_elem"));
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("mfma32_probe", &mfma32_probe, "32x32x16 bf16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 semantics probe");

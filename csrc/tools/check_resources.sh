@@ -10,7 +10,7 @@ cd "$(dirname "$0")/../.."
 if [ $# -gt 0 ]; then SRCS=("$@"); else
   SRCS=(csrc/fmha.hip csrc/wgemm.hip csrc/fgemm.hip csrc/probes.hip
         csrc/layernorm.hip csrc/gelu.hip csrc/dropout.hip
-        csrc/transpose.hip)
+        csrc/drop_path.hip csrc/transpose.hip)
 fi
 OUT=$(mktemp -d)
 trap 'rm -rf "$OUT"' EXIT

@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "csrc/fmha.hip",
         "csrc/gelu.hip",
         "csrc/dropout.hip",
+        "csrc/drop_path.hip",
         "csrc/transpose.hip",
         "csrc/wgemm.hip",
         "csrc/fgemm.hip",

@@ -7,6 +7,13 @@ reference flags.
 import argparse
 
 
+def _rate_below_one(text):
+    value = float(text)
+    if not 0.0 <= value < 1.0:
+        raise argparse.ArgumentTypeError(f"must be in [0, 1), got {text}")
+    return value
+
+
 def build_arg_parser():
     parser = argparse.ArgumentParser()
     # data / io (reference run_vit_training.py:329-336)
@@ -78,6 +85,13 @@ def build_arg_parser():
         "(hidden, stream) pairs and every residual add is fused into "
         "the following LayerNorm kernel (identical math/rounding; no "
         "standalone elementwise add kernels remain)",
+    )
+    parser.add_argument(
+        "--drop_path_rate", type=_rate_below_one, default=0.0,
+        help="stochastic depth: block i of N drops each of its two "
+        "residual branches per sample with probability "
+        "rate * i / (N - 1) in training and scales a kept branch by the "
+        "inverse keep probability (timm's drop_path_rate); 0 <= rate < 1",
     )
     parser.add_argument(
         "--profile", action="store_true", dest="profile",

@@ -30,7 +30,8 @@ import torch.nn as nn
 from .. import dist as xdist
 from ..ops import (  # noqa: F401
     HiddenDropout, LayerNorm, NativeLinear, attention_qkv, cross_entropy,
-    dropout_add, fused_add_layer_norm, gelu_dropout, hidden_dropout,
+    drop_path, drop_path_add, dropout_add, fused_add_layer_norm,
+    gelu_dropout, hidden_dropout,
 )
 
 
@@ -103,7 +104,9 @@ class Attention(nn.Module):
         self.proj = NativeLinear(dim, dim)
         self.proj_drop = HiddenDropout(proj_drop)
 
-    def forward(self, x):
+    def forward(self, x, skip_proj_drop=False):
+        """skip_proj_drop: return the projection output BEFORE proj_drop;
+        the block then folds that dropout into its drop_path pass."""
         B, T, E = x.shape
         # [B, T, 3, H, d] is a free view of the fused projection; the
         # attention core reads q/k/v through strides and returns [B, T, E]
@@ -116,7 +119,8 @@ class Attention(nn.Module):
             dropout_p=self.attn_drop_p,
             training=self.training,
         )
-        return self.proj_drop(self.proj(o))
+        o = self.proj(o)
+        return o if skip_proj_drop else self.proj_drop(o)
 
 
 class Mlp(nn.Module):
@@ -146,8 +150,14 @@ class Mlp(nn.Module):
 
 class Block(nn.Module):
     """Pre-LN transformer block: x + Attn(LN1(x)); x + MLP(LN2(x))
-    (timm Block as configured at reference run_vit_training.py:134-141;
-    drop_path unused there, so none here).
+    (timm Block as configured at reference run_vit_training.py:134-141).
+
+    drop_path (unused by the reference, default 0) is timm's stochastic
+    depth: in training each of the two branches is dropped per sample
+    with that probability and scaled by 1 / (1 - drop_path) otherwise,
+    after the branch's own dropout and with an independent mask each
+    (ops.drop_path / ops.drop_path_add, one fused pass per branch).  At 0
+    the block runs exactly the statements it ran without it.
 
     Two interfaces, identical math:
       * default: tensor -> tensor, with the attention residual add fused
@@ -162,9 +172,16 @@ class Block(nn.Module):
     """
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True,
-                 drop=0.0, attn_drop=0.0, deferred_residual=False):
+                 drop=0.0, attn_drop=0.0, deferred_residual=False,
+                 drop_path=0.0):
         super().__init__()
+        if drop_path < 0 or drop_path >= 1:
+            raise ValueError(
+                f"drop_path probability has to be in [0, 1), but got "
+                f"{drop_path}"
+            )
         self.deferred_residual = deferred_residual
+        self.drop_path = drop_path
         self.norm1 = LayerNorm(dim, eps=1e-6)
         self.attn = Attention(
             dim, num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop
@@ -172,17 +189,32 @@ class Block(nn.Module):
         self.norm2 = LayerNorm(dim, eps=1e-6)
         self.mlp = Mlp(dim, int(dim * mlp_ratio), drop=drop)
 
+    def extra_repr(self):
+        return f"drop_path={self.drop_path}"
+
+    def _attn_branch(self, normed):
+        if self.drop_path == 0.0:
+            return self.attn(normed)
+        # proj_drop and the per-sample mask in one pass
+        return drop_path(
+            self.attn(normed, skip_proj_drop=True), self.drop_path,
+            self.training, p_elem=self.attn.proj_drop.p,
+        )
+
     def forward(self, x):
         if self.deferred_residual:
             return self._forward_deferred(x)
-        attn_out = self.attn(self.norm1(x))
+        attn_out = self._attn_branch(self.norm1(x))
         # fused residual add + norm2 (one kernel for x+attn_out and its LN)
         x, normed = fused_add_layer_norm(
             x, attn_out, self.norm2.weight, self.norm2.bias, self.norm2.eps
         )
         # MLP residual add with fc2's dropout folded in
         mlp_out, p = self.mlp(normed)
-        return dropout_add(x, mlp_out, p, self.training)
+        if self.drop_path == 0.0:
+            return dropout_add(x, mlp_out, p, self.training)
+        return drop_path_add(
+            x, mlp_out, self.drop_path, self.training, p_elem=p)
 
     def _forward_deferred(self, x):
         if isinstance(x, (tuple, list)):
@@ -194,12 +226,15 @@ class Block(nn.Module):
             )
         else:  # first block: nothing pending
             s0, y0 = x, self.norm1(x)
-        attn_out = self.attn(y0)
+        attn_out = self._attn_branch(y0)
         s1, y1 = fused_add_layer_norm(
             s0, attn_out, self.norm2.weight, self.norm2.bias, self.norm2.eps
         )
         mlp_out, p = self.mlp(y1)
-        return hidden_dropout(mlp_out, p, self.training), s1
+        if self.drop_path == 0.0:
+            return hidden_dropout(mlp_out, p, self.training), s1
+        return drop_path(
+            mlp_out, self.drop_path, self.training, p_elem=p), s1
 
 
 class FSDPViTModel(nn.Module):
@@ -223,6 +258,7 @@ class FSDPViTModel(nn.Module):
         grad_ckpt_wrap,
         fsdp_wrap,
         fuse_residual=False,
+        drop_path_rate=0.0,
     ):
         super().__init__()
         self.fuse_residual = fuse_residual
@@ -247,6 +283,9 @@ class FSDPViTModel(nn.Module):
                 drop=mlp_dropout,
                 attn_drop=att_dropout,
                 deferred_residual=fuse_residual,
+                # timm's linspace(0, rate, num_blocks): block 0 never
+                # drops, the last block drops at the full rate
+                drop_path=drop_path_rate * idx / max(num_blocks - 1, 1),
             )
             # init BEFORE wrapping: FSDP shards the weights at wrap time
             init_vit_weights(block)
@@ -355,6 +394,7 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
         grad_ckpt_wrap=grad_ckpt_wrap,
         fsdp_wrap=fsdp_wrap,
         fuse_residual=getattr(cfg, "fuse_residual", False),
+        drop_path_rate=getattr(cfg, "drop_path_rate", 0.0),
     )
     # root wrap without grad-ckpt (reference run_vit_training.py:197-199)
     model = fsdp_wrap(model)

@@ -12,6 +12,10 @@ from .dropout import (
     gelu_dropout_reference, hidden_dropout, hidden_dropout_mask,
     hidden_dropout_reference,
 )
+from .drop_path import (
+    drop_path, drop_path_add, drop_path_add_reference, drop_path_mask,
+    drop_path_reference,
+)
 
 __all__ = [
     "ext",
@@ -40,4 +44,9 @@ __all__ = [
     "hidden_dropout_reference",
     "dropout_add_reference",
     "gelu_dropout_reference",
+    "drop_path",
+    "drop_path_add",
+    "drop_path_mask",
+    "drop_path_reference",
+    "drop_path_add_reference",
 ]
