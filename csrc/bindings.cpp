@@ -56,6 +56,12 @@ torch::Tensor fmha_bwd_qkv(torch::Tensor dout, torch::Tensor qkv,
                            long num_heads, double scale, double p_drop,
                            long seed);
 torch::Tensor fmha_rowdot(torch::Tensor dout, torch::Tensor o);
+std::vector<torch::Tensor> qk_norm_fwd(torch::Tensor qkv, torch::Tensor wq,
+                                       torch::Tensor bq, torch::Tensor wk,
+                                       torch::Tensor bk, double eps);
+std::vector<torch::Tensor> qk_norm_bwd(torch::Tensor dqkv, torch::Tensor qkv,
+                                       torch::Tensor wq, torch::Tensor wk,
+                                       torch::Tensor mean, torch::Tensor rstd);
 std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x);
 std::vector<torch::Tensor> gelu_bwd_colsum_t(torch::Tensor dy,
                                              torch::Tensor x);
@@ -146,6 +152,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Delta = rowsum(dO * O) of the attention backward, fp32 [B,H,T], "
         "for contiguous [B,H,T,D] operands",
         py::arg("dout"), py::arg("o"));
+  m.def("qk_norm_fwd", &qk_norm_fwd,
+        "(out, mean, rstd): per-head LayerNorm over D on slices 0 (q) and 1 "
+        "(k) of the fused projection [B,T,3,H,D], each with its own bf16 "
+        "[D] weight and bias; slice 2 (v) is copied bit for bit, so "
+        "fmha_fwd_qkv reads out unchanged; mean/rstd are fp32 [B,T,2,H]; "
+        "D in {32, 64, 96, 128, 160, 192}",
+        py::arg("qkv"), py::arg("wq"), py::arg("bq"), py::arg("wk"),
+        py::arg("bk"), py::arg("eps"));
+  m.def("qk_norm_bwd", &qk_norm_bwd,
+        "(dwq, dbq, dwk, dbk): backward of qk_norm_fwd; dqkv (the gradient "
+        "of out) is OVERWRITTEN IN PLACE on slices 0 and 1 with the "
+        "gradient of qkv, slice 2 is neither read nor written; the "
+        "parameter gradients are fixed-order fp32 sums rounded to bf16 [D]",
+        py::arg("dqkv"), py::arg("qkv"), py::arg("wq"), py::arg("wk"),
+        py::arg("mean"), py::arg("rstd"));
   m.def("gelu_bwd_colsum", &gelu_bwd_colsum,
         "(dx, colsum): exact-erf GELU backward and the bf16 column sums "
         "of dx over all rows (fc1 bias gradient) in one pass",

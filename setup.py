@@ -23,6 +23,7 @@ ext = CUDAExtension(
         "csrc/adamw.hip",
         "csrc/cross_entropy.hip",
         "csrc/fmha.hip",
+        "csrc/qk_norm.hip",
         "csrc/gelu.hip",
         "csrc/dropout.hip",
         "csrc/drop_path.hip",

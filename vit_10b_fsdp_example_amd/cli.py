@@ -94,6 +94,13 @@ def build_arg_parser():
         "inverse keep probability (timm's drop_path_rate); 0 <= rate < 1",
     )
     parser.add_argument(
+        "--qk_norm", action="store_true", dest="qk_norm",
+        help="LayerNorm over head_dim on q and on k before the dot product "
+        "(ViT-22B's remedy for attention-logit growth, timm's qk_norm): "
+        "adds attn.q_norm / attn.k_norm to every block, 4 * head_dim "
+        "parameters each, so checkpoints with and without it differ",
+    )
+    parser.add_argument(
         "--profile", action="store_true", dest="profile",
         help="profile a few early steps with torch.profiler (CPU+GPU "
         "kernel timeline) and write a chrome trace + a top-kernel table "

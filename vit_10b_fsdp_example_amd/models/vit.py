@@ -89,9 +89,15 @@ class PatchEmbed(nn.Module):
 class Attention(nn.Module):
     """Pre-projection multi-head attention matching timm 0.4.12's module
     (fused qkv Linear with bias, per-head scaled dot product, attention
-    dropout, output projection + dropout)."""
+    dropout, output projection + dropout).
 
-    def __init__(self, dim, num_heads, qkv_bias=True, attn_drop=0.0, proj_drop=0.0):
+    qk_norm (timm's flag of that name, ViT-22B's remedy for attention-
+    logit growth): a LayerNorm over head_dim on q and on k before the dot
+    product, its parameters shared by all heads.  q_norm and k_norm exist
+    only when it is on."""
+
+    def __init__(self, dim, num_heads, qkv_bias=True, attn_drop=0.0,
+                 proj_drop=0.0, qk_norm=False):
         super().__init__()
         assert dim % num_heads == 0
         self.num_heads = num_heads
@@ -103,6 +109,10 @@ class Attention(nn.Module):
         self.attn_drop_p = attn_drop
         self.proj = NativeLinear(dim, dim)
         self.proj_drop = HiddenDropout(proj_drop)
+        self.qk_norm = qk_norm
+        if qk_norm:
+            self.q_norm = LayerNorm(self.head_dim, eps=1e-6)
+            self.k_norm = LayerNorm(self.head_dim, eps=1e-6)
 
     def forward(self, x, skip_proj_drop=False):
         """skip_proj_drop: return the projection output BEFORE proj_drop;
@@ -112,12 +122,17 @@ class Attention(nn.Module):
         # attention core reads q/k/v through strides and returns [B, T, E]
         # directly (no permute/contiguous copies around the kernel)
         qkv = self.qkv(x).reshape(B, T, 3, self.num_heads, self.head_dim)
+        qk_norm = None
+        if self.qk_norm:
+            qk_norm = (self.q_norm.weight, self.q_norm.bias,
+                       self.k_norm.weight, self.k_norm.bias, self.q_norm.eps)
         o = attention_qkv(
             qkv,
             self.num_heads,
             scale=self.scale,
             dropout_p=self.attn_drop_p,
             training=self.training,
+            qk_norm=qk_norm,
         )
         o = self.proj(o)
         return o if skip_proj_drop else self.proj_drop(o)
@@ -173,7 +188,7 @@ class Block(nn.Module):
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True,
                  drop=0.0, attn_drop=0.0, deferred_residual=False,
-                 drop_path=0.0):
+                 drop_path=0.0, qk_norm=False):
         super().__init__()
         if drop_path < 0 or drop_path >= 1:
             raise ValueError(
@@ -184,7 +199,8 @@ class Block(nn.Module):
         self.drop_path = drop_path
         self.norm1 = LayerNorm(dim, eps=1e-6)
         self.attn = Attention(
-            dim, num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop
+            dim, num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop,
+            proj_drop=drop, qk_norm=qk_norm,
         )
         self.norm2 = LayerNorm(dim, eps=1e-6)
         self.mlp = Mlp(dim, int(dim * mlp_ratio), drop=drop)
@@ -259,6 +275,7 @@ class FSDPViTModel(nn.Module):
         fsdp_wrap,
         fuse_residual=False,
         drop_path_rate=0.0,
+        qk_norm=False,
     ):
         super().__init__()
         self.fuse_residual = fuse_residual
@@ -286,6 +303,7 @@ class FSDPViTModel(nn.Module):
                 # timm's linspace(0, rate, num_blocks): block 0 never
                 # drops, the last block drops at the full rate
                 drop_path=drop_path_rate * idx / max(num_blocks - 1, 1),
+                qk_norm=qk_norm,
             )
             # init BEFORE wrapping: FSDP shards the weights at wrap time
             init_vit_weights(block)
@@ -321,9 +339,10 @@ class FSDPViTModel(nn.Module):
 
 
 def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
-                     num_classes, in_chans=3):
+                     num_classes, in_chans=3, num_heads=None, qk_norm=False):
     """Exact parameter count for the architecture (used by tests; the
-    10B default config gives 10,077,917,160 — SURVEY.md §2D)."""
+    10B default config gives 10,077,917,160 — SURVEY.md §2D).  qk_norm
+    adds q_norm and k_norm, 4 * head_dim per block, and needs num_heads."""
     e = embed_dim
     hid = int(e * mlp_ratio)
     t = (image_size // patch_size) ** 2
@@ -334,6 +353,8 @@ def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
         + hid * e + e
         + 4 * e
     )
+    if qk_norm:
+        per_block += 4 * (e // num_heads)
     patch_embed = (in_chans * patch_size * patch_size) * e + e
     pos_embed = t * e
     final_norm = 2 * e
@@ -395,6 +416,7 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
         fsdp_wrap=fsdp_wrap,
         fuse_residual=getattr(cfg, "fuse_residual", False),
         drop_path_rate=getattr(cfg, "drop_path_rate", 0.0),
+        qk_norm=getattr(cfg, "qk_norm", False),
     )
     # root wrap without grad-ckpt (reference run_vit_training.py:197-199)
     model = fsdp_wrap(model)

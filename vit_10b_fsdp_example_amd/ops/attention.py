@@ -133,13 +133,58 @@ class _FlashAttentionQkvFn(torch.autograd.Function):
         return dqkv, None, None, None, None
 
 
-def attention_qkv(qkv, num_heads, scale=None, dropout_p=0.0, training=False):
+# head dims csrc/qk_norm.hip is instantiated for
+QK_NORM_HEAD_DIMS = (32, 64, 96, 128, 160, 192)
+
+
+class _QkNormFlashAttentionQkvFn(torch.autograd.Function):
+    """--qk_norm: per-head LayerNorm of q and k (csrc/qk_norm.hip) and the
+    strided flash attention as ONE node.  The norm writes [B,T,3,H,D]
+    again (v copied through), so the attention kernels run unchanged.
+
+    Backward: fmha_bwd_qkv allocates dqkv, nothing outside this function
+    has seen it, and qk_norm_bwd turns its q and k slices into the
+    gradient of the projection IN PLACE; dv never moves.  Two nodes would
+    have to hand a fresh tensor from one to the other."""
+
+    @staticmethod
+    def forward(ctx, qkv, wq, bq, wk, bk, eps, num_heads, scale, p_drop,
+                seed):
+        qkv_n, mean, rstd = ext().qk_norm_fwd(qkv, wq, bq, wk, bk, eps)
+        o, lse = ext().fmha_fwd_qkv(qkv_n, num_heads, scale, p_drop, seed)
+        ctx.save_for_backward(qkv, wq, wk, mean, rstd, qkv_n, o, lse)
+        ctx.num_heads = num_heads
+        ctx.scale = scale
+        ctx.p_drop = p_drop
+        ctx.seed = seed
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, wq, wk, mean, rstd, qkv_n, o, lse = ctx.saved_tensors
+        dqkv = ext().fmha_bwd_qkv(
+            do.contiguous(), qkv_n, o, lse, ctx.num_heads, ctx.scale,
+            ctx.p_drop, ctx.seed,
+        )
+        dwq, dbq, dwk, dbk = ext().qk_norm_bwd(dqkv, qkv, wq, wk, mean, rstd)
+        return dqkv, dwq, dbq, dwk, dbk, None, None, None, None, None
+
+
+def attention_qkv(qkv, num_heads, scale=None, dropout_p=0.0, training=False,
+                  qk_norm=None):
     """Attention on the fused qkv projection.
 
     qkv: [B, T, 3, H, D] (a free reshape view of the qkv Linear output);
     returns [B, T, H*D].  GPU bf16 uses the strided flash kernels with
     in-kernel attention dropout; the fallback path permutes to
     [B, H, T, D] and runs the math composition.
+
+    qk_norm: None, or (wq, bq, wk, bk, eps): LayerNorm over D of every
+    head of q and of k, each with its own [D] weight and bias, before the
+    dot product (ViT-22B; timm's qk_norm).  GPU bf16 with bf16 parameters
+    and D in QK_NORM_HEAD_DIMS runs the qk_norm kernels; everything else
+    normalises the q and k views with F.layer_norm and goes on as without
+    it.
     """
     B, T, three, H, D = qkv.shape
     assert three == 3 and H == num_heads
@@ -150,6 +195,21 @@ def attention_qkv(qkv, num_heads, scale=None, dropout_p=0.0, training=False):
         and use_hip(qkv)
         and hasattr(ext(), "fmha_fwd_qkv")
     )
+    if qk_norm is not None:
+        wq, bq, wk, bk, eps = qk_norm
+        if (use_kernel and D in QK_NORM_HEAD_DIMS
+                and all(_kernel_dtype(t.dtype) for t in (wq, bq, wk, bk))):
+            p = dropout_p if training else 0.0
+            seed = _draw_seed() if p > 0.0 else 0
+            return _QkNormFlashAttentionQkvFn.apply(
+                qkv.contiguous(), wq.contiguous(), bq.contiguous(),
+                wk.contiguous(), bk.contiguous(), eps, num_heads, scale, p,
+                seed,
+            )
+        q, k, v = qkv.unbind(2)
+        q = torch.nn.functional.layer_norm(q, (D,), wq, bq, eps)
+        k = torch.nn.functional.layer_norm(k, (D,), wk, bk, eps)
+        qkv = torch.stack((q, k, v), dim=2)
     if use_kernel:
         p = dropout_p if training else 0.0
         seed = _draw_seed() if p > 0.0 else 0
