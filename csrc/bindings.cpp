@@ -84,6 +84,18 @@ torch::Tensor drop_path_fwd(torch::Tensor x, long n_samples, double p_path,
 torch::Tensor drop_path_add_fwd(torch::Tensor x, torch::Tensor res,
                                 long n_samples, double p_path, long seed_path,
                                 double p_elem, long seed_elem);
+torch::Tensor layer_scale_fwd(torch::Tensor x, torch::Tensor gamma,
+                              long n_samples, double p_path, long seed_path,
+                              double p_elem, long seed_elem);
+torch::Tensor layer_scale_add_fwd(torch::Tensor x, torch::Tensor res,
+                                  torch::Tensor gamma, long n_samples,
+                                  double p_path, long seed_path, double p_elem,
+                                  long seed_elem);
+std::vector<torch::Tensor> layer_scale_bwd(torch::Tensor dy,
+                                           torch::Tensor branch,
+                                           torch::Tensor gamma, long n_samples,
+                                           double p_path, long seed_path,
+                                           double p_elem, long seed_elem);
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma32_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor tr16_probe(long mode);
@@ -222,6 +234,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("res"), py::arg("n_samples"),
         py::arg("p_path"), py::arg("seed_path"), py::arg("p_elem"),
         py::arg("seed_elem"));
+  m.def("layer_scale_fwd", &layer_scale_fwd,
+        "LayerScale on a residual branch with its element dropout and "
+        "stochastic depth folded in: keep ? x * gamma[c] / ((1 - p_path)"
+        "(1 - p_elem)) : 0 under drop_path_fwd's masks; either probability "
+        "may be 0 (a pure per-channel scale at both 0); a dropped sample's "
+        "rows are not read",
+        py::arg("x"), py::arg("gamma"), py::arg("n_samples"),
+        py::arg("p_path"), py::arg("seed_path"), py::arg("p_elem"),
+        py::arg("seed_elem"));
+  m.def("layer_scale_add_fwd", &layer_scale_add_fwd,
+        "x + layer_scale_fwd(res, gamma, ...) in one pass, rounded once; "
+        "where dropped, x passes through bit for bit and res is not read "
+        "under a dropped sample",
+        py::arg("x"), py::arg("res"), py::arg("gamma"), py::arg("n_samples"),
+        py::arg("p_path"), py::arg("seed_path"), py::arg("p_elem"),
+        py::arg("seed_elem"));
+  m.def("layer_scale_bwd", &layer_scale_bwd,
+        "(dbranch, dgamma): backward of both forwards from one read of dy "
+        "and branch: dbranch = layer_scale_fwd(dy, gamma, ...), dgamma[c] = "
+        "the masked, scaled column sums of dy * branch in fp32 and a fixed "
+        "order (bit-reproducible), rounded to bf16 [C]; a dropped sample's "
+        "rows of dy and branch are not read",
+        py::arg("dy"), py::arg("branch"), py::arg("gamma"),
+        py::arg("n_samples"), py::arg("p_path"), py::arg("seed_path"),
+        py::arg("p_elem"), py::arg("seed_elem"));
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("mfma32_probe", &mfma32_probe, "32x32x16 bf16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 semantics probe");

@@ -27,6 +27,7 @@ ext = CUDAExtension(
         "csrc/gelu.hip",
         "csrc/dropout.hip",
         "csrc/drop_path.hip",
+        "csrc/layer_scale.hip",
         "csrc/transpose.hip",
         "csrc/wgemm.hip",
         "csrc/fgemm.hip",

@@ -14,6 +14,13 @@ def _rate_below_one(text):
     return value
 
 
+def _non_negative(text):
+    value = float(text)
+    if not value >= 0.0:
+        raise argparse.ArgumentTypeError(f"must be >= 0, got {text}")
+    return value
+
+
 def build_arg_parser():
     parser = argparse.ArgumentParser()
     # data / io (reference run_vit_training.py:329-336)
@@ -99,6 +106,14 @@ def build_arg_parser():
         "(ViT-22B's remedy for attention-logit growth, timm's qk_norm): "
         "adds attn.q_norm / attn.k_norm to every block, 4 * head_dim "
         "parameters each, so checkpoints with and without it differ",
+    )
+    parser.add_argument(
+        "--layer_scale_init", type=_non_negative, default=0.0,
+        help="LayerScale (CaiT, timm's init_values): multiply each of a "
+        "block's two residual branches by a learnable per-channel vector "
+        "initialised to this value, x + drop_path(gamma * dropout(branch)); "
+        "0 turns it off; > 0 adds ls1.gamma / ls2.gamma to every block, "
+        "2 * embed_dim parameters, so checkpoints with and without it differ",
     )
     parser.add_argument(
         "--profile", action="store_true", dest="profile",

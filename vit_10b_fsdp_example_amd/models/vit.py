@@ -31,7 +31,7 @@ from .. import dist as xdist
 from ..ops import (  # noqa: F401
     HiddenDropout, LayerNorm, NativeLinear, attention_qkv, cross_entropy,
     drop_path, drop_path_add, dropout_add, fused_add_layer_norm,
-    gelu_dropout, hidden_dropout,
+    gelu_dropout, hidden_dropout, layer_scale, layer_scale_add,
 )
 
 
@@ -163,6 +163,21 @@ class Mlp(nn.Module):
         return self.fc2(x), p
 
 
+class LayerScale(nn.Module):
+    """Learnable per-channel scale of a residual branch (CaiT; timm's
+    module and parameter name, so blocks.N.ls1.gamma / ls2.gamma match
+    timm checkpoints).  Block does not call it: it hands gamma to
+    ops.layer_scale / ops.layer_scale_add, which fold the scale into the
+    branch's dropout, drop-path and residual-add pass."""
+
+    def __init__(self, dim, init):
+        super().__init__()
+        self.gamma = nn.Parameter(torch.full((dim,), float(init)))
+
+    def forward(self, x):
+        return layer_scale(x, self.gamma, self.training)
+
+
 class Block(nn.Module):
     """Pre-LN transformer block: x + Attn(LN1(x)); x + MLP(LN2(x))
     (timm Block as configured at reference run_vit_training.py:134-141).
@@ -173,6 +188,14 @@ class Block(nn.Module):
     after the branch's own dropout and with an independent mask each
     (ops.drop_path / ops.drop_path_add, one fused pass per branch).  At 0
     the block runs exactly the statements it ran without it.
+
+    layer_scale_init (timm's init_values, default 0 = off): with a value
+    > 0 each branch is multiplied by a learnable per-channel vector
+    (ls1.gamma, ls2.gamma) initialised to it, between the branch's
+    dropout and its drop-path mask: x + drop_path(gamma * dropout(branch)).
+    The scale, both masks and the MLP residual add are one pass
+    (ops.layer_scale / ops.layer_scale_add).  At 0 neither module exists
+    and the block runs exactly the statements it ran without it.
 
     Two interfaces, identical math:
       * default: tensor -> tensor, with the attention residual add fused
@@ -188,8 +211,12 @@ class Block(nn.Module):
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True,
                  drop=0.0, attn_drop=0.0, deferred_residual=False,
-                 drop_path=0.0, qk_norm=False):
+                 drop_path=0.0, qk_norm=False, layer_scale_init=0.0):
         super().__init__()
+        if layer_scale_init < 0:
+            raise ValueError(
+                f"layer_scale_init has to be >= 0, but got {layer_scale_init}"
+            )
         if drop_path < 0 or drop_path >= 1:
             raise ValueError(
                 f"drop_path probability has to be in [0, 1), but got "
@@ -204,11 +231,22 @@ class Block(nn.Module):
         )
         self.norm2 = LayerNorm(dim, eps=1e-6)
         self.mlp = Mlp(dim, int(dim * mlp_ratio), drop=drop)
+        self.layer_scale_init = layer_scale_init
+        if layer_scale_init > 0:
+            self.ls1 = LayerScale(dim, layer_scale_init)
+            self.ls2 = LayerScale(dim, layer_scale_init)
 
     def extra_repr(self):
         return f"drop_path={self.drop_path}"
 
     def _attn_branch(self, normed):
+        if self.layer_scale_init > 0:
+            # gamma, proj_drop and the per-sample mask in one pass
+            return layer_scale(
+                self.attn(normed, skip_proj_drop=True), self.ls1.gamma,
+                self.training, p_path=self.drop_path,
+                p_elem=self.attn.proj_drop.p,
+            )
         if self.drop_path == 0.0:
             return self.attn(normed)
         # proj_drop and the per-sample mask in one pass
@@ -227,6 +265,10 @@ class Block(nn.Module):
         )
         # MLP residual add with fc2's dropout folded in
         mlp_out, p = self.mlp(normed)
+        if self.layer_scale_init > 0:
+            return layer_scale_add(
+                x, mlp_out, self.ls2.gamma, self.training,
+                p_path=self.drop_path, p_elem=p)
         if self.drop_path == 0.0:
             return dropout_add(x, mlp_out, p, self.training)
         return drop_path_add(
@@ -247,6 +289,10 @@ class Block(nn.Module):
             s0, attn_out, self.norm2.weight, self.norm2.bias, self.norm2.eps
         )
         mlp_out, p = self.mlp(y1)
+        if self.layer_scale_init > 0:
+            return layer_scale(
+                mlp_out, self.ls2.gamma, self.training,
+                p_path=self.drop_path, p_elem=p), s1
         if self.drop_path == 0.0:
             return hidden_dropout(mlp_out, p, self.training), s1
         return drop_path(
@@ -276,6 +322,7 @@ class FSDPViTModel(nn.Module):
         fuse_residual=False,
         drop_path_rate=0.0,
         qk_norm=False,
+        layer_scale_init=0.0,
     ):
         super().__init__()
         self.fuse_residual = fuse_residual
@@ -304,6 +351,7 @@ class FSDPViTModel(nn.Module):
                 # drops, the last block drops at the full rate
                 drop_path=drop_path_rate * idx / max(num_blocks - 1, 1),
                 qk_norm=qk_norm,
+                layer_scale_init=layer_scale_init,
             )
             # init BEFORE wrapping: FSDP shards the weights at wrap time
             init_vit_weights(block)
@@ -339,10 +387,12 @@ class FSDPViTModel(nn.Module):
 
 
 def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
-                     num_classes, in_chans=3, num_heads=None, qk_norm=False):
+                     num_classes, in_chans=3, num_heads=None, qk_norm=False,
+                     layer_scale=False):
     """Exact parameter count for the architecture (used by tests; the
     10B default config gives 10,077,917,160 — SURVEY.md §2D).  qk_norm
-    adds q_norm and k_norm, 4 * head_dim per block, and needs num_heads."""
+    adds q_norm and k_norm, 4 * head_dim per block, and needs num_heads;
+    layer_scale adds ls1.gamma and ls2.gamma, 2 * embed_dim per block."""
     e = embed_dim
     hid = int(e * mlp_ratio)
     t = (image_size // patch_size) ** 2
@@ -355,6 +405,8 @@ def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
     )
     if qk_norm:
         per_block += 4 * (e // num_heads)
+    if layer_scale:
+        per_block += 2 * e
     patch_embed = (in_chans * patch_size * patch_size) * e + e
     pos_embed = t * e
     final_norm = 2 * e
@@ -417,6 +469,7 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
         fuse_residual=getattr(cfg, "fuse_residual", False),
         drop_path_rate=getattr(cfg, "drop_path_rate", 0.0),
         qk_norm=getattr(cfg, "qk_norm", False),
+        layer_scale_init=getattr(cfg, "layer_scale_init", 0.0),
     )
     # root wrap without grad-ckpt (reference run_vit_training.py:197-199)
     model = fsdp_wrap(model)

@@ -16,6 +16,10 @@ from .drop_path import (
     drop_path, drop_path_add, drop_path_add_reference, drop_path_mask,
     drop_path_reference,
 )
+from .layer_scale import (
+    layer_scale, layer_scale_add, layer_scale_add_reference,
+    layer_scale_bwd_reference, layer_scale_reference,
+)
 
 __all__ = [
     "ext",
@@ -49,4 +53,9 @@ __all__ = [
     "drop_path_mask",
     "drop_path_reference",
     "drop_path_add_reference",
+    "layer_scale",
+    "layer_scale_add",
+    "layer_scale_reference",
+    "layer_scale_add_reference",
+    "layer_scale_bwd_reference",
 ]
