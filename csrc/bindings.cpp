@@ -71,6 +71,7 @@ std::vector<torch::Tensor> gelu_dropout_bwd_colsum(torch::Tensor dy,
 std::vector<torch::Tensor> gelu_dropout_bwd_colsum_t(torch::Tensor dy,
                                                      torch::Tensor x, double p,
                                                      long seed);
+torch::Tensor gelu_fwd_t(torch::Tensor x);
 torch::Tensor transpose2d(torch::Tensor x);
 std::vector<torch::Tensor> transpose_colsum(torch::Tensor x);
 torch::Tensor dropout_fwd(torch::Tensor x, double p, long seed);
@@ -187,6 +188,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(dx, colsum, dx^T): gelu_bwd_colsum with dx^T [hid, rows] as a "
         "third output; dx and colsum are bit-identical to gelu_bwd_colsum's",
         py::arg("dy"), py::arg("x"));
+  m.def("gelu_fwd_t", &gelu_fwd_t,
+        "bf16 x [R, C] contiguous -> gelu(x)^T [C, R] contiguous "
+        "(C % 8 == 0), bit-identical to F.gelu(x).t().contiguous(): one "
+        "read of x, one write of the result",
+        py::arg("x"));
   m.def("transpose2d", &transpose2d,
         "bf16 [R, C] contiguous -> [C, R] contiguous (C % 8 == 0)",
         py::arg("x"));

@@ -27,7 +27,10 @@
 
 #include "colsum_final.h"  // partials -> bf16 sums, shared with transpose.hip
 #include "common.h"
-#include "gelu_math.h"  // gelu_bwd_one, shared with dropout.hip
+#include "gelu_math.h"  // gelu_bwd_one, gelu_erf_f32: shared with dropout.hip
+#ifndef VITFSDP_KERNELS_ONLY
+#include "transpose.h"  // transpose_plan: gelu_fwd_t moves transpose.hip's tiles
+#endif
 
 namespace {
 
@@ -188,6 +191,89 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
   if (c0 + t < hid) part[(long)blockIdx.y * hid + c0 + t] = acc;
 }
 
+// gelu(x)^T [cols, rows] from x [rows, cols]: the act^T operand of fc2's TN
+// weight gradient rebuilt from the saved pre-activation, so that the
+// forward's gelu(x) need not be kept for the backward (ops/linear.py,
+// mlp_fc2_recompute_act).  transpose.hip's plain kernel with the GELU
+// applied between the 16-byte load and the LDS write: same 64 x 64 tiles,
+// slot swizzle, 128-byte output segments, grid and ragged-edge guards.
+// Each element is torch's F.gelu in bits: the exact-erf form in fp32,
+// rounded once to bf16.
+//
+// Compiled without packed fp32 VALU ops (v_pk_mul/add/fma_f32), which the
+// compiler may pair the eight elements of a vector into.  __syncthreads
+// is a header function, compiled with the default target features, and
+// would be called instead of inlined from here: the barrier is by builtin
+// (as in qk_norm.hip).
+constexpr int kFTile = 64;
+constexpr int kFSlots = kFTile / 8;
+
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+#ifdef __HIP_DEVICE_COMPILE__
+__attribute__((target("no-packed-fp32-ops")))
+#endif
+__global__ __launch_bounds__(kBlock) void gelu_fwd_t_kernel(
+    const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
+    long R, long C, int tiles_per_block) {
+  __shared__ ushort8_t tile[kFTile * kFSlots];
+  const unsigned short* tile_s = reinterpret_cast<const unsigned short*>(tile);
+  const int t = threadIdx.x;
+  // load phase: lane -> input row hi + 32k, 16-byte column slot lo;
+  // store phase: lane -> input column hi + 32k, 8-row group lo
+  const int hi = t >> 3, lo = t & 7;
+  const long c0 = (long)blockIdx.x * kFTile;
+  const bool col_ok = c0 + lo * 8 < C;
+  const bool vec_store = (R & 7) == 0;  // output rows 16-byte aligned
+
+  const long tile_begin = (long)blockIdx.y * tiles_per_block;
+  for (int it = 0; it < tiles_per_block; ++it) {
+    const long r0 = (tile_begin + it) * kFTile;
+    if (r0 >= R) break;  // block-uniform
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int r = hi + 32 * k;
+      // rows and columns outside the tensor are not written to the tile;
+      // the store phase reads none of them
+      if (col_ok && r0 + r < R) {
+        const ushort8_t v =
+            *reinterpret_cast<const ushort8_t*>(x + (r0 + r) * C + c0 + lo * 8);
+        ushort8_t g;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          g[j] = f32_to_bf16(gelu_erf_f32(bf16_to_f32(v[j])));
+        tile[r * kFSlots + (lo ^ ((r >> 3) & 7))] = g;
+      }
+    }
+    lds_barrier();
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int c = hi + 32 * k;
+      const long r = r0 + lo * 8;
+      if (c0 + c < C && r < R) {
+        const unsigned short* src =
+            tile_s + (lo * 8) * kFTile + ((c >> 3) ^ lo) * 8 + (c & 7);
+        unsigned short* dst = y + (c0 + c) * R + r;
+        if (vec_store) {  // then r + 8 <= R
+          ushort8_t o;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o[j] = src[j * kFTile];
+          *reinterpret_cast<ushort8_t*>(dst) = o;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (r + j < R) dst[j] = src[j * kFTile];
+        }
+      }
+    }
+    lds_barrier();
+  }
+}
+
 #ifdef VITFSDP_KERNELS_ONLY
 // explicit instantiations so -Rpass-analysis reports every kernel
 #define VITFSDP_INSTANTIATE_DGELU(DROP_)                                     \
@@ -312,6 +398,30 @@ std::vector<torch::Tensor> gelu_dropout_bwd_colsum_t(torch::Tensor dy,
                                                      long seed) {
   return gelu_bwd_colsum_run<true>("gelu_dropout_bwd_colsum", dy, x, true, p,
                                    seed);
+}
+
+// x: bf16 [rows, cols] contiguous, cols % 8 == 0.  Returns gelu(x)^T
+// [cols, rows] contiguous, each element F.gelu's (exact erf) in bits.
+torch::Tensor gelu_fwd_t(torch::Tensor x) {
+  const char* op = "gelu_fwd_t";
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2, op, ": 2-D GPU tensor expected");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, op, ": bf16 only");
+  TORCH_CHECK(x.is_contiguous(), op,
+              ": input must be contiguous (no silent copy)");
+  const long R = x.size(0), C = x.size(1);
+  TORCH_CHECK(C > 0 && C % 8 == 0, op,
+              ": columns must be a multiple of 8, got ", C);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, op,
+              ": input must be 16-byte aligned");
+  auto y = torch::empty({C, R}, x.options());
+  if (R == 0) return y;
+  const TransposePlan p = transpose_plan(R, C, op);
+  hipLaunchKernelGGL(gelu_fwd_t_kernel, p.grid, dim3(kBlock), 0,
+                     at::cuda::getCurrentCUDAStream(),
+                     (const unsigned short*)x.data_ptr(),
+                     (unsigned short*)y.data_ptr(), R, C, p.tpb);
+  HIP_CHECK_LAST();
+  return y;
 }
 #endif  // VITFSDP_KERNELS_ONLY
 

@@ -119,15 +119,6 @@ template __global__ void transpose_kernel<true>(const unsigned short*,
 }  // namespace
 
 #ifndef VITFSDP_KERNELS_ONLY
-namespace {
-
-// Grid of both kernel variants for an [R, C] input.
-struct TransposePlan {
-  dim3 grid;
-  int tpb;        // 64-row tiles per block
-  long n_chunks;  // grid.y, rows of the column-sum partials
-};
-
 TransposePlan transpose_plan(long R, long C, const char* what) {
   const long col_tiles = (C + kTile - 1) / kTile;
   const long row_tiles = (R + kTile - 1) / kTile;
@@ -140,8 +131,6 @@ TransposePlan transpose_plan(long R, long C, const char* what) {
               ": tensor too large");
   return {dim3((unsigned)col_tiles, (unsigned)n_chunks), tpb, n_chunks};
 }
-
-}  // namespace
 
 void transpose2d_launch(const void* x, void* y, long R, long C,
                         hipStream_t stream, const char* what) {

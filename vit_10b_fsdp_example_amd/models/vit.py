@@ -33,6 +33,8 @@ from ..ops import (  # noqa: F401
     drop_path, drop_path_add, dropout_add, fused_add_layer_norm,
     gelu_dropout, hidden_dropout, layer_scale, layer_scale_add,
 )
+from ..ops.linear import mlp_fc2_recompute_act, mlp_recompute_act_on
+from ..parallel.checkpoint import in_checkpoint_region, n_open_mlp_blocks
 
 
 def init_vit_weights(module, recursive=False):
@@ -159,8 +161,13 @@ class Mlp(nn.Module):
 
     def forward(self, x):
         p = self.drop.p
-        x = gelu_dropout(self.fc1(x), p, self.training)
-        return self.fc2(x), p
+        h = self.fc1(x)
+        # outside a checkpoint region gelu(h) is not kept for the backward
+        # but rebuilt from h there (ops/linear.py mlp_fc2_recompute_act)
+        if (torch.is_grad_enabled() and mlp_recompute_act_on(p)
+                and not in_checkpoint_region()):
+            return mlp_fc2_recompute_act(self.fc2, h), p
+        return self.fc2(gelu_dropout(h, p, self.training)), p
 
 
 class LayerScale(nn.Module):
@@ -256,15 +263,39 @@ class Block(nn.Module):
         )
 
     def forward(self, x):
-        if self.deferred_residual:
-            return self._forward_deferred(x)
-        attn_out = self._attn_branch(self.norm1(x))
+        return self.mlp_half(*self.attn_half(x))
+
+    def attn_half(self, x):
+        """Everything up to and including norm2: (stream, norm2 output).
+        The checkpoint wrapper's open-MLP form checkpoints this alone."""
+        if self.deferred_residual and isinstance(x, (tuple, list)):
+            hidden, stream = x
+            # previous block's MLP residual add, fused into our norm1
+            s0, y0 = fused_add_layer_norm(
+                stream, hidden, self.norm1.weight, self.norm1.bias,
+                self.norm1.eps,
+            )
+        else:  # plain interface, or first block: nothing pending
+            s0, y0 = x, self.norm1(x)
+        attn_out = self._attn_branch(y0)
         # fused residual add + norm2 (one kernel for x+attn_out and its LN)
-        x, normed = fused_add_layer_norm(
-            x, attn_out, self.norm2.weight, self.norm2.bias, self.norm2.eps
+        return fused_add_layer_norm(
+            s0, attn_out, self.norm2.weight, self.norm2.bias, self.norm2.eps
         )
-        # MLP residual add with fc2's dropout folded in
+
+    def mlp_half(self, x, normed):
+        """The MLP branch on attn_half's pair; returns what forward does."""
         mlp_out, p = self.mlp(normed)
+        if self.deferred_residual:
+            if self.layer_scale_init > 0:
+                return layer_scale(
+                    mlp_out, self.ls2.gamma, self.training,
+                    p_path=self.drop_path, p_elem=p), x
+            if self.drop_path == 0.0:
+                return hidden_dropout(mlp_out, p, self.training), x
+            return drop_path(
+                mlp_out, self.drop_path, self.training, p_elem=p), x
+        # MLP residual add with fc2's dropout folded in
         if self.layer_scale_init > 0:
             return layer_scale_add(
                 x, mlp_out, self.ls2.gamma, self.training,
@@ -273,30 +304,6 @@ class Block(nn.Module):
             return dropout_add(x, mlp_out, p, self.training)
         return drop_path_add(
             x, mlp_out, self.drop_path, self.training, p_elem=p)
-
-    def _forward_deferred(self, x):
-        if isinstance(x, (tuple, list)):
-            hidden, stream = x
-            # previous block's MLP residual add, fused into our norm1
-            s0, y0 = fused_add_layer_norm(
-                stream, hidden, self.norm1.weight, self.norm1.bias,
-                self.norm1.eps,
-            )
-        else:  # first block: nothing pending
-            s0, y0 = x, self.norm1(x)
-        attn_out = self._attn_branch(y0)
-        s1, y1 = fused_add_layer_norm(
-            s0, attn_out, self.norm2.weight, self.norm2.bias, self.norm2.eps
-        )
-        mlp_out, p = self.mlp(y1)
-        if self.layer_scale_init > 0:
-            return layer_scale(
-                mlp_out, self.ls2.gamma, self.training,
-                p_path=self.drop_path, p_elem=p), s1
-        if self.drop_path == 0.0:
-            return hidden_dropout(mlp_out, p, self.training), s1
-        return drop_path(
-            mlp_out, self.drop_path, self.training, p_elem=p), s1
 
 
 class FSDPViTModel(nn.Module):
@@ -443,6 +450,15 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
     # the 288 GB of HBM3E).  -1 = every block, the reference behavior.
     ckpt_limit = getattr(cfg, "grad_ckpt_blocks", -1)
     ckpt_count = {"i": 0}
+    # the first n_open of the checkpointed blocks checkpoint only their
+    # attention half: what the others save by not keeping gelu(h) pays
+    # for their MLP activations (parallel/checkpoint.py)
+    n_open = 0
+    if cfg.grad_ckpt and mlp_recompute_act_on(cfg.mlp_dropout):
+        n_open = n_open_mlp_blocks(
+            cfg.num_blocks,
+            cfg.num_blocks if ckpt_limit < 0 else ckpt_limit,
+            cfg.embed_dim, int(cfg.embed_dim * cfg.mlp_ratio))
 
     def grad_ckpt_wrap(module):
         if not cfg.grad_ckpt:
@@ -451,7 +467,7 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
         ckpt_count["i"] += 1
         if 0 <= ckpt_limit <= idx:
             return module
-        return checkpoint_module(module)
+        return checkpoint_module(module, open_mlp=idx < n_open)
 
     model = FSDPViTModel(
         image_size=cfg.image_size,

@@ -131,11 +131,13 @@ def _wgrad_mm_shapes_ok(m, n, k):
             and (m // 256) * (n // 256) >= _MIN_TILES)
 
 
-def _wgrad_mm_dims(at, b):
+def _wgrad_mm_dims(at, b, b_t_ok=False):
     """(m, n, k) if mm(at, b) has the layout of the weight-gradient GEMM
     AddmmBackward emits — first operand a transposed view of a
     contiguous [K, M] base, second operand contiguous [K, N] — else
-    None."""
+    None.  With ``b_t_ok`` the second operand may also be a transposed
+    view of a contiguous [N, K] tensor (an activation that was rebuilt
+    transposed, see mlp_fc2_recompute_act)."""
     if at.dim() != 2 or b.dim() != 2 or at.shape[1] != b.shape[0]:
         return None
     m, k = at.shape
@@ -143,9 +145,16 @@ def _wgrad_mm_dims(at, b):
         return None  # degenerate strides are ambiguous
     if not (at.stride(0) == 1 and at.stride(1) == m):
         return None
-    if not (b.stride(1) == 1 and b.stride(0) == b.shape[1]):
+    if not (b.stride(1) == 1 and b.stride(0) == b.shape[1]) and not (
+            b_t_ok and _is_t_of_contiguous(b)):
         return None
     return m, b.shape[1], k
+
+
+def _is_t_of_contiguous(b):
+    """b [K, N] is the transposed view of a contiguous [N, K] tensor (and,
+    with N >= 2, not row-contiguous itself)."""
+    return b.shape[1] >= 2 and b.stride(0) == 1 and b.stride(1) == b.shape[0]
 
 
 def _is_wgrad_mm(at, b):
@@ -220,7 +229,7 @@ def _tn_wgrad_out_ok(m, k):
 
 def _is_tn_wgrad_mm(at, b):
     """The weight-gradient GEMM, at a shape the TN route takes."""
-    dims = _wgrad_mm_dims(at, b)
+    dims = _wgrad_mm_dims(at, b, b_t_ok=True)
     return dims is not None and _tn_wgrad_shapes_ok(*dims)
 
 
@@ -866,7 +875,8 @@ class TunedGemmMode(TorchDispatchMode):
 
     def _tn_wgrad(self, at, x):
         """dW [out, in] contiguous = lt_gemm(dy^T, (x^T).t()).  The two
-        transposes live only until the GEMM is queued."""
+        transposes live only until the GEMM is queued.  x is [K, in]
+        contiguous, or the transposed view of a contiguous x^T."""
         dy = at.t()  # the contiguous [K, out] base
         st, self._tn_stash = self._tn_stash, None
         if st is not None and st[2] is not None and _same_buffer(dy, st[0]):
@@ -887,8 +897,11 @@ class TunedGemmMode(TorchDispatchMode):
             else:
                 dyT, colsum = self._call("transpose", dy, True)
                 self._tn_stash = (dy, colsum, None)
-        xT, _ = self._call("transpose", x, False)
-        b = xT.t()
+        if _op_layout(x) == "N":
+            xT, _ = self._call("transpose", x, False)
+            b = xT.t()
+        else:
+            b = x  # x^T is what its producer wrote: nothing to transpose
         idx = self._tuned_index(_dual_key(dyT, b))
         self.tn_hits += 1
         return self._call("gemm", dyT, b, -1 if idx is None else idx, None)
@@ -916,6 +929,95 @@ class TunedGemmMode(TorchDispatchMode):
         idx = self._tuned_index(("T", "N", inn, dy.shape[0], out))
         self.tn_dgrad_hits += 1
         return self._call("dgrad", dy, w, -1 if idx is None else idx)
+
+
+# --------------------------------------------------------------------------
+# fc2 without its saved input.  AddmmBackward of fc2 keeps act = gelu(h)
+# [rows, hid] as mat1 and reads it once, for the weight gradient; on the
+# TN route that GEMM does not even read act but act^T, which
+# transpose2d writes from it.  GeluBackward keeps h anyway, so under a
+# pair of saved-tensor hooks fc2's mat1 is packed as a handle on h and
+# unpacked as gelu(h) rebuilt: by _C.gelu_fwd_t as act^T, handed over as
+# its transposed view (one read of h and one write, what transpose2d
+# moved), where the weight gradient will take the TN route, by F.gelu
+# everywhere else.  The autograd nodes are the stock ones, so checkpoint
+# early-stop is untouched; per block, hid elements per token row less
+# are kept for the backward.
+#
+# Nested saved_tensors_hooks apply only the innermost pair, so inside a
+# checkpoint(use_reentrant=False) region these hooks would hide fc2's mat1
+# from the checkpoint and pin h through the handle: callers use this
+# only where the MLP runs outside such a region (models/vit.py Mlp,
+# parallel/checkpoint.py).  VITFSDP_MLP_RECOMPUTE_ACT=0 turns it off.
+# --------------------------------------------------------------------------
+
+
+def mlp_recompute_act_on(p_drop=0.0):
+    """Whether an MLP with this hidden dropout rebuilds gelu(h) in the
+    backward.  Off behind hidden dropout (fc2's saved input is then the
+    dropout's output) and with the fused fc1 epilogue (the GELU output
+    is then not made by an op on h; asked of the switch alone, since the
+    MLP dims are not registered before the first Mlp is built).
+    Environment and arguments only: the same on every rank."""
+    return (os.environ.get("VITFSDP_MLP_RECOMPUTE_ACT", "1") != "0"
+            and p_drop == 0
+            and os.environ.get("VITFSDP_FUSED_GELU", "0") != "1")
+
+
+class _ActHandle:
+    """What fc2's mat1 is packed as: the pre-activation (detached, the
+    storage GeluBackward holds) and the shape mat1 had."""
+
+    __slots__ = ("h", "shape")
+
+    def __init__(self, h, shape):
+        self.h, self.shape = h, shape
+
+
+def _tn_mode():
+    """The innermost active TunedGemmMode if its TN weight-gradient route
+    runs on the real kernels, else None."""
+    from torch.utils._python_dispatch import _get_current_dispatch_mode_stack
+
+    for m in reversed(_get_current_dispatch_mode_stack()):
+        if isinstance(m, TunedGemmMode):
+            ok = m.tn_wgrad and not m._fakes
+            return m if ok else None
+    return None
+
+
+def _rebuild_act(h, shape, d_out):
+    """gelu(h) with that shape for fc2's weight gradient [d_out, hid]."""
+    with torch.no_grad():
+        if (len(shape) == 2 and shape[0] >= 2 and d_out >= 2
+                and _tn_wgrad_shapes_ok(d_out, shape[1], shape[0])
+                and h.is_contiguous() and h.data_ptr() % 16 == 0
+                and _tn_mode() is not None and _hip_bf16(h)):
+            return ext().gelu_fwd_t(h.view(shape)).t()
+        return F.gelu(h).view(shape)
+
+
+def mlp_fc2_recompute_act(fc2, h):
+    """fc2(gelu(h)) whose graph keeps h where it would keep gelu(h)."""
+    act = F.gelu(h)
+    # the hooks outlive this call with the graph: they must not hold act
+    ptr, numel = act.untyped_storage().data_ptr(), act.numel()
+    h_saved, d_out = h.detach(), fc2.weight.shape[0]
+
+    def pack(t):
+        if (t.numel() == numel and t.dtype == h_saved.dtype
+                and t.is_contiguous()
+                and t.untyped_storage().data_ptr() == ptr):
+            return _ActHandle(h_saved, tuple(t.shape))
+        return t
+
+    def unpack(o):
+        if isinstance(o, _ActHandle):
+            return _rebuild_act(o.h, o.shape, d_out)
+        return o
+
+    with torch.autograd.graph.saved_tensors_hooks(pack, unpack):
+        return fc2(act)
 
 
 def gemm_dispatch_context():
