@@ -72,6 +72,12 @@ std::vector<torch::Tensor> gelu_dropout_bwd_colsum_t(torch::Tensor dy,
                                                      torch::Tensor x, double p,
                                                      long seed);
 torch::Tensor gelu_fwd_t(torch::Tensor x);
+torch::Tensor swiglu_fwd(torch::Tensor h, double p, long seed);
+std::vector<torch::Tensor> swiglu_bwd_colsum(torch::Tensor da, torch::Tensor h,
+                                             double p, long seed);
+std::vector<torch::Tensor> swiglu_bwd_colsum_t(torch::Tensor da,
+                                               torch::Tensor h);
+torch::Tensor swiglu_fwd_t(torch::Tensor h);
 torch::Tensor transpose2d(torch::Tensor x);
 std::vector<torch::Tensor> transpose_colsum(torch::Tensor x);
 torch::Tensor dropout_fwd(torch::Tensor x, double p, long seed);
@@ -193,6 +199,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(C % 8 == 0), bit-identical to F.gelu(x).t().contiguous(): one "
         "read of x, one write of the result",
         py::arg("x"));
+  m.def("swiglu_fwd", &swiglu_fwd,
+        "bf16 h [.., 2H] -> dropout(silu(h[.., :H]) * h[.., H:]) [.., H] in "
+        "one pass (H % 8 == 0), fp32 arithmetic, rounded once; p == 0 is no "
+        "dropout, else the (seed, row, col) hash mask",
+        py::arg("h"), py::arg("p"), py::arg("seed"));
+  m.def("swiglu_bwd_colsum", &swiglu_bwd_colsum,
+        "(dh, colsum): backward of swiglu_fwd from da [.., H] and h, mask "
+        "and scale applied here, and the bf16 column sums of dh [2H] over "
+        "all rows (fc1 bias gradient) in one pass",
+        py::arg("da"), py::arg("h"), py::arg("p"), py::arg("seed"));
+  m.def("swiglu_bwd_colsum_t", &swiglu_bwd_colsum_t,
+        "(dh, colsum, dh^T): swiglu_bwd_colsum at p == 0 with dh^T [2H, rows] "
+        "as a third output; dh and colsum are bit-identical to "
+        "swiglu_bwd_colsum's",
+        py::arg("da"), py::arg("h"));
+  m.def("swiglu_fwd_t", &swiglu_fwd_t,
+        "bf16 h [R, 2H] contiguous -> swiglu_fwd(h, 0, 0)^T [H, R] "
+        "contiguous, equal in bits: one read of h, one write of the result",
+        py::arg("h"));
   m.def("transpose2d", &transpose2d,
         "bf16 [R, C] contiguous -> [C, R] contiguous (C % 8 == 0)",
         py::arg("x"));

@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "csrc/fmha.hip",
         "csrc/qk_norm.hip",
         "csrc/gelu.hip",
+        "csrc/swiglu.hip",
         "csrc/dropout.hip",
         "csrc/drop_path.hip",
         "csrc/layer_scale.hip",

@@ -116,6 +116,16 @@ def build_arg_parser():
         "2 * embed_dim parameters, so checkpoints with and without it differ",
     )
     parser.add_argument(
+        "--mlp_type", choices=("gelu", "swiglu"), default="gelu",
+        help="the block's MLP: gelu is fc1 -> GELU -> fc2 with hidden width "
+        "embed_dim * mlp_ratio; swiglu is the gated MLP of recent large "
+        "ViTs, a = silu(h[..., :H]) * h[..., H:] on h = fc1(x) [.., 2H] with "
+        "H = embed_dim * mlp_ratio * 2 / 3 rounded up to a multiple of 256.  "
+        "The parameter names are the same (mlp.fc1, mlp.fc2) but the shapes "
+        "differ, so a checkpoint written with one type does not load with "
+        "the other",
+    )
+    parser.add_argument(
         "--profile", action="store_true", dest="profile",
         help="profile a few early steps with torch.profiler (CPU+GPU "
         "kernel timeline) and write a chrome trace + a top-kernel table "

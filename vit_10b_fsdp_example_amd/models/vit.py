@@ -24,6 +24,8 @@ default init and only pos_embed gets trunc_normal(std=0.02).  Pass
 recursive=True to init_vit_weights for the "intended" behavior.
 """
 
+import os
+
 import torch
 import torch.nn as nn
 
@@ -31,7 +33,8 @@ from .. import dist as xdist
 from ..ops import (  # noqa: F401
     HiddenDropout, LayerNorm, NativeLinear, attention_qkv, cross_entropy,
     drop_path, drop_path_add, dropout_add, fused_add_layer_norm,
-    gelu_dropout, hidden_dropout, layer_scale, layer_scale_add,
+    gelu_dropout, hidden_dropout, layer_scale, layer_scale_add, swiglu,
+    swiglu_fc2_recompute, swiglu_hidden_dim,
 )
 from ..ops.linear import mlp_fc2_recompute_act, mlp_recompute_act_on
 from ..parallel.checkpoint import in_checkpoint_region, n_open_mlp_blocks
@@ -140,32 +143,62 @@ class Attention(nn.Module):
         return o if skip_proj_drop else self.proj_drop(o)
 
 
+MLP_TYPES = ("gelu", "swiglu")
+
+
 class Mlp(nn.Module):
     """fc1 -> GELU -> dropout -> fc2 -> dropout (timm Mlp).
 
     forward returns fc2's output BEFORE its dropout, together with the
     dropout probability: the block applies that dropout itself, fused
     into the residual add (ops.dropout_add) or, with the deferred
-    residual, as ops.hidden_dropout on the branch."""
+    residual, as ops.hidden_dropout on the branch.
 
-    def __init__(self, dim, hidden_dim, drop=0.0):
+    mlp_type "swiglu" is the gated MLP: fc1 is Linear(dim, 2 * hidden_dim),
+    and the activation silu(h[..., :hidden_dim]) * h[..., hidden_dim:],
+    gate half first (ops.swiglu, csrc/swiglu.hip).  The parameter names
+    are those of "gelu"; fc1's shapes differ."""
+
+    def __init__(self, dim, hidden_dim, drop=0.0, mlp_type="gelu"):
         super().__init__()
-        self.fc1 = NativeLinear(dim, hidden_dim)
+        if mlp_type not in MLP_TYPES:
+            raise ValueError(
+                f"mlp_type has to be one of {MLP_TYPES}, but got {mlp_type!r}"
+            )
+        self.mlp_type = mlp_type
+        gated = mlp_type == "swiglu"
+        if gated and os.environ.get("VITFSDP_FUSED_GELU", "0") == "1":
+            raise ValueError(
+                "VITFSDP_FUSED_GELU=1 fuses a GELU into fc1's epilogue and "
+                "cannot be combined with mlp_type 'swiglu'"
+            )
+        self.fc1 = NativeLinear(dim, 2 * hidden_dim if gated else hidden_dim)
         self.fc2 = NativeLinear(hidden_dim, dim)
         self.drop = HiddenDropout(drop)
-        # register the MLP dims so the GEMM dispatch router can fuse the
-        # GELU into the fc1/fc2 hipBLASLt epilogues (VITFSDP_FUSED_GELU)
-        from ..ops.linear import configure_gelu_fusion
+        from ..ops.linear import configure_gelu_fusion, configure_swiglu
 
-        configure_gelu_fusion(dim, hidden_dim)
+        if gated:
+            # fc1's input width, for the dh^T gate of the SwiGLU backward
+            configure_swiglu(dim)
+        else:
+            # register the MLP dims so the GEMM dispatch router can fuse
+            # the GELU into the fc1/fc2 hipBLASLt epilogues
+            # (VITFSDP_FUSED_GELU)
+            configure_gelu_fusion(dim, hidden_dim)
 
     def forward(self, x):
         p = self.drop.p
         h = self.fc1(x)
-        # outside a checkpoint region gelu(h) is not kept for the backward
-        # but rebuilt from h there (ops/linear.py mlp_fc2_recompute_act)
-        if (torch.is_grad_enabled() and mlp_recompute_act_on(p)
-                and not in_checkpoint_region()):
+        # outside a checkpoint region the activation is not kept for the
+        # backward but rebuilt from h there (ops/linear.py
+        # mlp_fc2_recompute_act)
+        recompute = (torch.is_grad_enabled() and mlp_recompute_act_on(p)
+                     and not in_checkpoint_region())
+        if self.mlp_type == "swiglu":
+            if recompute:
+                return swiglu_fc2_recompute(self.fc2, h), p
+            return self.fc2(swiglu(h, p, self.training)), p
+        if recompute:
             return mlp_fc2_recompute_act(self.fc2, h), p
         return self.fc2(gelu_dropout(h, p, self.training)), p
 
@@ -218,7 +251,8 @@ class Block(nn.Module):
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True,
                  drop=0.0, attn_drop=0.0, deferred_residual=False,
-                 drop_path=0.0, qk_norm=False, layer_scale_init=0.0):
+                 drop_path=0.0, qk_norm=False, layer_scale_init=0.0,
+                 mlp_type="gelu"):
         super().__init__()
         if layer_scale_init < 0:
             raise ValueError(
@@ -237,7 +271,9 @@ class Block(nn.Module):
             proj_drop=drop, qk_norm=qk_norm,
         )
         self.norm2 = LayerNorm(dim, eps=1e-6)
-        self.mlp = Mlp(dim, int(dim * mlp_ratio), drop=drop)
+        hidden_dim = (swiglu_hidden_dim(dim, mlp_ratio)
+                      if mlp_type == "swiglu" else int(dim * mlp_ratio))
+        self.mlp = Mlp(dim, hidden_dim, drop=drop, mlp_type=mlp_type)
         self.layer_scale_init = layer_scale_init
         if layer_scale_init > 0:
             self.ls1 = LayerScale(dim, layer_scale_init)
@@ -330,6 +366,7 @@ class FSDPViTModel(nn.Module):
         drop_path_rate=0.0,
         qk_norm=False,
         layer_scale_init=0.0,
+        mlp_type="gelu",
     ):
         super().__init__()
         self.fuse_residual = fuse_residual
@@ -359,6 +396,7 @@ class FSDPViTModel(nn.Module):
                 drop_path=drop_path_rate * idx / max(num_blocks - 1, 1),
                 qk_norm=qk_norm,
                 layer_scale_init=layer_scale_init,
+                mlp_type=mlp_type,
             )
             # init BEFORE wrapping: FSDP shards the weights at wrap time
             init_vit_weights(block)
@@ -395,18 +433,24 @@ class FSDPViTModel(nn.Module):
 
 def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
                      num_classes, in_chans=3, num_heads=None, qk_norm=False,
-                     layer_scale=False):
+                     layer_scale=False, mlp_type="gelu"):
     """Exact parameter count for the architecture (used by tests; the
     10B default config gives 10,077,917,160 — SURVEY.md §2D).  qk_norm
     adds q_norm and k_norm, 4 * head_dim per block, and needs num_heads;
-    layer_scale adds ls1.gamma and ls2.gamma, 2 * embed_dim per block."""
+    layer_scale adds ls1.gamma and ls2.gamma, 2 * embed_dim per block;
+    mlp_type "swiglu" has fc1 [2H, e] and fc2 [e, H] with
+    H = swiglu_hidden_dim(e, mlp_ratio)."""
     e = embed_dim
     hid = int(e * mlp_ratio)
+    fc1_out = hid
+    if mlp_type == "swiglu":
+        hid = swiglu_hidden_dim(e, mlp_ratio)
+        fc1_out = 2 * hid
     t = (image_size // patch_size) ** 2
     per_block = (
         e * 3 * e + 3 * e
         + e * e + e
-        + e * hid + hid
+        + e * fc1_out + fc1_out
         + hid * e + e
         + 4 * e
     )
@@ -454,11 +498,18 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
     # attention half: what the others save by not keeping gelu(h) pays
     # for their MLP activations (parallel/checkpoint.py)
     n_open = 0
+    mlp_type = getattr(cfg, "mlp_type", "gelu")
     if cfg.grad_ckpt and mlp_recompute_act_on(cfg.mlp_dropout):
+        hidden_dim = int(cfg.embed_dim * cfg.mlp_ratio)
+        kept_dim = hidden_dim
+        if mlp_type == "swiglu":
+            # H is freed, h [.., 2H] is kept
+            hidden_dim = swiglu_hidden_dim(cfg.embed_dim, cfg.mlp_ratio)
+            kept_dim = 2 * hidden_dim
         n_open = n_open_mlp_blocks(
             cfg.num_blocks,
             cfg.num_blocks if ckpt_limit < 0 else ckpt_limit,
-            cfg.embed_dim, int(cfg.embed_dim * cfg.mlp_ratio))
+            cfg.embed_dim, hidden_dim, kept_dim)
 
     def grad_ckpt_wrap(module):
         if not cfg.grad_ckpt:
@@ -486,6 +537,7 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
         drop_path_rate=getattr(cfg, "drop_path_rate", 0.0),
         qk_norm=getattr(cfg, "qk_norm", False),
         layer_scale_init=getattr(cfg, "layer_scale_init", 0.0),
+        mlp_type=mlp_type,
     )
     # root wrap without grad-ckpt (reference run_vit_training.py:197-199)
     model = fsdp_wrap(model)

@@ -20,6 +20,10 @@ from .layer_scale import (
     layer_scale, layer_scale_add, layer_scale_add_reference,
     layer_scale_bwd_reference, layer_scale_reference,
 )
+from .swiglu import (
+    swiglu, swiglu_bwd_reference, swiglu_fc2_recompute, swiglu_hidden_dim,
+    swiglu_reference,
+)
 
 __all__ = [
     "ext",
@@ -58,4 +62,9 @@ __all__ = [
     "layer_scale_reference",
     "layer_scale_add_reference",
     "layer_scale_bwd_reference",
+    "swiglu",
+    "swiglu_fc2_recompute",
+    "swiglu_hidden_dim",
+    "swiglu_reference",
+    "swiglu_bwd_reference",
 ]

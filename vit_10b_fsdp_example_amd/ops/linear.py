@@ -501,6 +501,34 @@ _LIB = torch.library.Library("vitfsdp", "DEF")
 _LIB.define(
     "gelu_dropout_bwd(Tensor dy, Tensor x, float p, int seed) -> Tensor")
 
+# --------------------------------------------------------------------------
+# The same for the gated MLP (--mlp_type swiglu, ops/swiglu.py).  Its
+# backward, dh [.., 2H] from da [.., H] and h = fc1(x), is the registered
+# op below for the reason gelu_dropout_bwd is one; ops/swiglu.py registers
+# its implementations and issues it, with p == 0 too.  The route answers
+# it with _C.swiglu_bwd_colsum, whose dh is the op's own, or, where fc1's
+# weight gradient takes the TN route and p == 0, with
+# _C.swiglu_bwd_colsum_t, and parks (dh, colsum, dh^T or None) in the same
+# stash.  VITFSDP_FUSED_DGELU_DBIAS alone governs it: the op names the
+# MLP's backward by itself, so no dims need to be registered to recognise
+# it.  What is registered (configure_swiglu, by a SwiGLU Mlp) is fc1's
+# input width, which the shape gate of dh^T asks for and which brings the
+# mode up in gemm_dispatch_context.
+# --------------------------------------------------------------------------
+
+_LIB.define("swiglu_bwd(Tensor da, Tensor h, float p, int seed) -> Tensor")
+
+_SWIGLU_CFG = {"d": 0}
+
+
+def configure_swiglu(embed_dim):
+    """Register fc1's input width of the SwiGLU MLP."""
+    _SWIGLU_CFG["d"] = int(embed_dim)
+
+
+def _dswiglu_dbias_switch():
+    return os.environ.get("VITFSDP_FUSED_DGELU_DBIAS", "1") != "0"
+
 
 # --------------------------------------------------------------------------
 # The extension kernels behind the routes of TunedGemmMode, under the
@@ -531,6 +559,15 @@ def _gelu_dropout_bwd_colsum(dy, x, p, seed, want_t):
     return dx, colsum, None
 
 
+def _swiglu_bwd_colsum(da, h, p, seed, want_t):
+    """(dh, bf16 column sums of dh, dh^T contiguous or None); dh^T with
+    p == 0 only."""
+    if want_t:
+        return ext().swiglu_bwd_colsum_t(da, h)
+    dh, colsum = ext().swiglu_bwd_colsum(da, h, p, seed)
+    return dh, colsum, None
+
+
 def _transposed(t, want_colsum):
     """(t^T contiguous, bf16 column sums of t or None)."""
     if want_colsum:
@@ -546,6 +583,7 @@ def _dgrad_tn(dy, w, idx):
 
 _KERNELS = {"gemm": _lt_gemm, "dgelu": _gelu_bwd_colsum,
             "dgelu_drop": _gelu_dropout_bwd_colsum,
+            "dswiglu": _swiglu_bwd_colsum,
             "transpose": _transposed, "dgrad": _dgrad_tn}
 
 # what an op method of TunedGemmMode returns for "not mine: run the stock op"
@@ -577,7 +615,7 @@ class TunedGemmMode(TorchDispatchMode):
 
     def __init__(self, table=None, native_wgrad=None, handler=None,
                  dgelu_handler=None, tn_handler=None, dgrad_handler=None,
-                 *, dgelu_drop_handler=None):
+                 *, dgelu_drop_handler=None, dswiglu_handler=None):
         super().__init__()
         self.table = lt_algo_table() if table is None else table
         self.native_wgrad = (
@@ -587,11 +625,13 @@ class TunedGemmMode(TorchDispatchMode):
         # and lifts the GPU gate for it, so that the routing logic runs
         # on the CPU.  Signatures as in _KERNELS, except that the dgelu
         # fake is dgelu_handler(dy, x) -> (dx, colsum) and the dgelu_drop
-        # fake dgelu_drop_handler(dy, x, p, seed) -> (dx, colsum), and
+        # fake dgelu_drop_handler(dy, x, p, seed) -> (dx, colsum), the
+        # dswiglu fake dswiglu_handler(da, h, p, seed) -> (dh, colsum), and
         # that the gemm fake also stands in for _C.fwd_gemm_gelu when
         # called with idx == "gelu" (-> (gelu output, pre-activation)).
         fakes = {"gemm": handler, "dgelu": dgelu_handler,
                  "dgelu_drop": dgelu_drop_handler,
+                 "dswiglu": dswiglu_handler,
                  "transpose": tn_handler, "dgrad": dgrad_handler}
         self._fakes = {k: f for k, f in fakes.items() if f is not None}
 
@@ -615,10 +655,13 @@ class TunedGemmMode(TorchDispatchMode):
         self.fused_dgelu = on(_dgelu_dbias_on(), "dgelu")
         # the same behind hidden dropout (vitfsdp::gelu_dropout_bwd)
         self.fused_dgelu_drop = on(_dgelu_dbias_on(), "dgelu_drop")
-        # (dx, colsum, dx^T or None) of either route: at most one entry
+        # the SwiGLU MLP's backward (vitfsdp::swiglu_bwd)
+        self.fused_dswiglu = on(_dswiglu_dbias_switch(), "dswiglu")
+        # (dx, colsum, dx^T or None) of any of the three: at most one entry
         self._dgelu_stash = None
         self.dgelu_hits = 0
         self.dgelu_drop_hits = 0
+        self.dswiglu_hits = 0
         self.dbias_hits = 0
         # TN weight gradients (see module comment above); the GEMM goes
         # through the gemm seam
@@ -732,6 +775,12 @@ class TunedGemmMode(TorchDispatchMode):
             return self._fused_dgelu_drop(*args)
         return _STOCK  # the implementation ops/dropout.py registered
 
+    def _swiglu_bwd(self, args, kwargs):
+        if (self.fused_dswiglu and len(args) == 4 and not kwargs
+                and self._is_mlp_dswiglu(*args[:2])):
+            return self._fused_dswiglu(*args)
+        return _STOCK  # the implementation ops/swiglu.py registered
+
     def _take_parked(self, stash, t):
         """The column sums parked in that stash if t is the tensor they
         were taken from (which empties the stash), else None."""
@@ -783,6 +832,7 @@ class TunedGemmMode(TorchDispatchMode):
         torch.ops.aten.gelu.default: _gelu,
         torch.ops.aten.gelu_backward.default: _gelu_backward,
         torch.ops.vitfsdp.gelu_dropout_bwd.default: _gelu_dropout_bwd,
+        torch.ops.vitfsdp.swiglu_bwd.default: _swiglu_bwd,
         torch.ops.aten.sum.dim_IntList: _sum,
     }
 
@@ -870,6 +920,46 @@ class TunedGemmMode(TorchDispatchMode):
         dx = self._dgelu_kernel("dgelu_drop", dy, x, float(p), int(seed))
         self.dgelu_drop_hits += 1
         return dx
+
+    # -- SwiGLU backward helpers ----------------------------------------------
+
+    def _is_mlp_dswiglu(self, da, h):
+        """da [.., H] and h [.., 2H] as the kernel takes them."""
+        hid = da.shape[-1] if da.dim() else 0
+        if not (
+            da.dim() >= 2
+            and h.shape == da.shape[:-1] + (2 * hid,)
+            and da.is_contiguous() and h.is_contiguous()
+        ):
+            return False
+        # the kernel's rows are 16-byte vectors
+        return self._takes(
+            "dswiglu", da, h,
+            kernel_ok=(hid > 0 and hid % 8 == 0 and da.data_ptr() % 16 == 0
+                       and h.data_ptr() % 16 == 0))
+
+    def _wants_dswiglu_t(self, h, p):
+        """fc1's weight gradient [2H, d] will take the TN route and expects
+        dh^T from the backward: the conditions of _wants_dgelu_t, and
+        p == 0 (there is no DROP form of that kernel)."""
+        hid2 = h.shape[-1]
+        return (p == 0 and self.tn_dgelu_t and _SWIGLU_CFG["d"] > 0
+                and _tn_wgrad_shapes_ok(
+                    hid2, _SWIGLU_CFG["d"], h.numel() // hid2))
+
+    def _fused_dswiglu(self, da, h, p, seed):
+        p, seed = float(p), int(seed)
+        want_t = self._wants_dswiglu_t(h, p)
+        if "dswiglu" in self._fakes:  # (dh, colsum) only: dh^T in torch
+            dh, colsum = self._fakes["dswiglu"](da, h, p, seed)
+            dht = (dh.reshape(-1, h.shape[-1]).t().contiguous()
+                   if want_t else None)
+        else:
+            dh, colsum, dht = _KERNELS["dswiglu"](da, h, p, seed, want_t)
+        # as _dgelu_kernel: the bias sum and the TN GEMM find it here
+        self._dgelu_stash = (dh, colsum, dht)
+        self.dswiglu_hits += 1
+        return dh
 
     # -- TN weight-gradient helpers ------------------------------------------
 
@@ -986,20 +1076,30 @@ def _tn_mode():
     return None
 
 
+def _rebuild_transposed(h, shape, d_out):
+    """Whether the activation of that shape is to be rebuilt from h as its
+    transpose: fc2's weight gradient [d_out, shape[1]] will take the TN
+    route on the real kernels, and h is what those take."""
+    return (len(shape) == 2 and shape[0] >= 2 and d_out >= 2
+            and _tn_wgrad_shapes_ok(d_out, shape[1], shape[0])
+            and h.is_contiguous() and h.data_ptr() % 16 == 0
+            and _tn_mode() is not None and _hip_bf16(h))
+
+
 def _rebuild_act(h, shape, d_out):
     """gelu(h) with that shape for fc2's weight gradient [d_out, hid]."""
     with torch.no_grad():
-        if (len(shape) == 2 and shape[0] >= 2 and d_out >= 2
-                and _tn_wgrad_shapes_ok(d_out, shape[1], shape[0])
-                and h.is_contiguous() and h.data_ptr() % 16 == 0
-                and _tn_mode() is not None and _hip_bf16(h)):
+        if _rebuild_transposed(h, shape, d_out):
             return ext().gelu_fwd_t(h.view(shape)).t()
         return F.gelu(h).view(shape)
 
 
-def mlp_fc2_recompute_act(fc2, h):
-    """fc2(gelu(h)) whose graph keeps h where it would keep gelu(h)."""
-    act = F.gelu(h)
+def mlp_fc2_recompute_act(fc2, h, act_fn=F.gelu, rebuild=_rebuild_act):
+    """fc2(act_fn(h)) whose graph keeps h where it would keep act_fn(h):
+    ``rebuild(h, shape, d_out)`` makes the activation again in the
+    backward.  The defaults are the GELU MLP's; ops/swiglu.py passes the
+    gated MLP's pair."""
+    act = act_fn(h)
     # the hooks outlive this call with the graph: they must not hold act
     ptr, numel = act.untyped_storage().data_ptr(), act.numel()
     h_saved, d_out = h.detach(), fc2.weight.shape[0]
@@ -1013,7 +1113,7 @@ def mlp_fc2_recompute_act(fc2, h):
 
     def unpack(o):
         if isinstance(o, _ActHandle):
-            return _rebuild_act(o.h, o.shape, d_out)
+            return rebuild(o.h, o.shape, d_out)
         return o
 
     with torch.autograd.graph.saved_tensors_hooks(pack, unpack):
@@ -1029,7 +1129,8 @@ def gemm_dispatch_context():
     lives in TunedGemmMode and is active whenever that mode is; it does
     not bring the mode up on its own: with the tuned table disabled and
     the fused dgelu off, the step is the plain NativeWgradMode one."""
-    if lt_algo_table() or _gelu_fusion_on() or _dgelu_dbias_on():
+    if (lt_algo_table() or _gelu_fusion_on() or _dgelu_dbias_on()
+            or (_dswiglu_dbias_switch() and _SWIGLU_CFG["d"] > 0)):
         return TunedGemmMode()
     if _NATIVE_WGRAD_DISPATCH:
         return NativeWgradMode()  # backward-compatible, wgrad only

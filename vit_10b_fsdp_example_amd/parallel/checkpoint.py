@@ -43,24 +43,28 @@ def _as_region(fn):
     return run
 
 
-def n_open_mlp_blocks(n_blocks, n_ckpt, embed_dim, hidden_dim):
+def n_open_mlp_blocks(n_blocks, n_ckpt, embed_dim, hidden_dim, kept_dim=None):
     """How many of the n_ckpt checkpointed blocks run their MLP half
-    outside the checkpoint region, so that fc1 and the GELU are not
+    outside the checkpoint region, so that fc1 and the activation are not
     recomputed, without more saved activation memory than checkpointing
     them whole.
 
     Per token row, in elements: every block whose MLP runs outside a
-    region stops keeping gelu(h) (ops/linear.py mlp_fc2_recompute_act),
-    hidden_dim less for each of the n_blocks - n_ckpt blocks that are
-    not checkpointed; an opened block keeps the stream and the LN2
-    output (embed_dim each) and h (hidden_dim) that a block checkpointed
-    whole does not.  So what the former free pays for
-    floor((n_blocks - n_ckpt) * hidden_dim / (2 * embed_dim + hidden_dim))
+    region stops keeping the activation (ops/linear.py
+    mlp_fc2_recompute_act), hidden_dim less for each of the
+    n_blocks - n_ckpt blocks that are not checkpointed; an opened block
+    keeps the stream and the LN2 output (embed_dim each) and h (kept_dim)
+    that a block checkpointed whole does not.  kept_dim is hidden_dim for
+    the GELU MLP, the default, and twice that for the gated one, whose h
+    holds the gate and the value half.  So what the former free pays for
+    floor((n_blocks - n_ckpt) * hidden_dim / (2 * embed_dim + kept_dim))
     of the latter.  Model shape and checkpoint depth only: the same on
     every rank."""
+    if kept_dim is None:
+        kept_dim = hidden_dim
     n_ckpt = max(0, min(n_ckpt, n_blocks))
     freed = (n_blocks - n_ckpt) * hidden_dim
-    return min(n_ckpt, freed // (2 * embed_dim + hidden_dim))
+    return min(n_ckpt, freed // (2 * embed_dim + kept_dim))
 
 
 class CheckpointWrapper(nn.Module):
