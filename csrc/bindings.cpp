@@ -20,6 +20,16 @@ std::vector<torch::Tensor> layernorm_add_bwd(torch::Tensor dy,
                                              torch::Tensor w,
                                              torch::Tensor mean,
                                              torch::Tensor rstd);
+std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
+                                       double eps);
+std::vector<torch::Tensor> rmsnorm_add_fwd(torch::Tensor x, torch::Tensor res,
+                                           torch::Tensor w, double eps);
+std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
+                                       torch::Tensor w, torch::Tensor rstd);
+std::vector<torch::Tensor> rmsnorm_add_bwd(torch::Tensor dy,
+                                           torch::Tensor dsum,
+                                           torch::Tensor sum, torch::Tensor w,
+                                           torch::Tensor rstd);
 
 void fused_adamw(std::vector<torch::Tensor> params,
                  std::vector<torch::Tensor> grads,
@@ -131,6 +141,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused residual-add + LayerNorm forward");
   m.def("layernorm_add_bwd", &layernorm_add_bwd,
         "fused residual-add + LayerNorm backward");
+  m.def("rmsnorm_fwd", &rmsnorm_fwd,
+        "(y, rstd): y = x * rsqrt(mean(x^2 over D) + eps) * w for bf16 rows "
+        "with D % 8 == 0 and D <= 8192, fp32 arithmetic, rounded once; rstd "
+        "is fp32, one per row; each row is read once and held in registers",
+        py::arg("x"), py::arg("w"), py::arg("eps"));
+  m.def("rmsnorm_add_fwd", &rmsnorm_add_fwd,
+        "(sum, y, rstd): sum = bf16(x + res), bit-equal to torch's add, and "
+        "rmsnorm_fwd of it in the same pass",
+        py::arg("x"), py::arg("res"), py::arg("w"), py::arg("eps"));
+  m.def("rmsnorm_bwd", &rmsnorm_bwd,
+        "(dx, dw): backward of rmsnorm_fwd from one read of dy and x; dw is "
+        "a fixed-order fp32 column sum rounded to bf16 [D], zeros at 0 rows",
+        py::arg("dy"), py::arg("x"), py::arg("w"), py::arg("rstd"));
+  m.def("rmsnorm_add_bwd", &rmsnorm_add_bwd,
+        "(dx1, dx2, dw): backward of rmsnorm_add_fwd; dsum (the gradient of "
+        "sum) is added in fp32 before the one rounding, and the result is "
+        "written to two distinct buffers, the gradients of x and res",
+        py::arg("dy"), py::arg("dsum"), py::arg("sum"), py::arg("w"),
+        py::arg("rstd"));
   m.def("fused_adamw", &fused_adamw,
         "multi-tensor AdamW step (fp32 master, fp32/bf16 grads with "
         "folded prescale + deferred clip)",

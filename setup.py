@@ -20,6 +20,7 @@ ext = CUDAExtension(
         "csrc/bindings.cpp",
         "csrc/ltgemm.cpp",
         "csrc/layernorm.hip",
+        "csrc/rmsnorm.hip",
         "csrc/adamw.hip",
         "csrc/cross_entropy.hip",
         "csrc/fmha.hip",

@@ -126,6 +126,16 @@ def build_arg_parser():
         "the other",
     )
     parser.add_argument(
+        "--norm_type", choices=("layernorm", "rmsnorm"), default="layernorm",
+        help="the norm of blocks.N.norm1, blocks.N.norm2 and the final norm: "
+        "layernorm has weight and bias; rmsnorm is the norm of the LLM-style "
+        "ViTs that pair with the swiglu MLP, "
+        "y = x * rsqrt(mean(x^2) + 1e-6) * weight with no mean subtraction "
+        "and no bias.  --qk_norm keeps its per-head LayerNorm under either "
+        "value.  rmsnorm has no norm*.bias entries, so a checkpoint written "
+        "with one type does not load with the other",
+    )
+    parser.add_argument(
         "--profile", action="store_true", dest="profile",
         help="profile a few early steps with torch.profiler (CPU+GPU "
         "kernel timeline) and write a chrome trace + a top-kernel table "

@@ -32,9 +32,9 @@ import torch.nn as nn
 from .. import dist as xdist
 from ..ops import (  # noqa: F401
     HiddenDropout, LayerNorm, NativeLinear, attention_qkv, cross_entropy,
-    drop_path, drop_path_add, dropout_add, fused_add_layer_norm,
-    gelu_dropout, hidden_dropout, layer_scale, layer_scale_add, swiglu,
-    swiglu_fc2_recompute, swiglu_hidden_dim,
+    RMSNorm, drop_path, drop_path_add, dropout_add, fused_add_layer_norm,
+    fused_add_rms_norm, gelu_dropout, hidden_dropout, layer_scale,
+    layer_scale_add, swiglu, swiglu_fc2_recompute, swiglu_hidden_dim,
 )
 from ..ops.linear import mlp_fc2_recompute_act, mlp_recompute_act_on
 from ..parallel.checkpoint import in_checkpoint_region, n_open_mlp_blocks
@@ -56,6 +56,8 @@ def init_vit_weights(module, recursive=False):
         elif isinstance(m, (nn.LayerNorm, LayerNorm)):
             nn.init.ones_(m.weight)
             nn.init.zeros_(m.bias)
+        elif isinstance(m, RMSNorm):
+            nn.init.ones_(m.weight)
 
     if recursive:
         module.apply(_apply)
@@ -218,6 +220,30 @@ class LayerScale(nn.Module):
         return layer_scale(x, self.gamma, self.training)
 
 
+NORM_TYPES = ("layernorm", "rmsnorm")
+
+
+def make_norm(norm_type, dim):
+    """The norm module of blocks.N.norm1 / norm2 and the final norm."""
+    if norm_type not in NORM_TYPES:
+        raise ValueError(
+            f"norm_type has to be one of {NORM_TYPES}, but got {norm_type!r}"
+        )
+    if norm_type == "rmsnorm":
+        return RMSNorm(dim, eps=1e-6)
+    return LayerNorm(dim, eps=1e-6)
+
+
+def apply_norm(norm, x, res=None):
+    """The one seam to a norm module of either type: norm(x), or with res
+    the fused pair (x + res, norm(x + res))."""
+    if res is None:
+        return norm(x)
+    if isinstance(norm, RMSNorm):
+        return fused_add_rms_norm(x, res, norm.weight, norm.eps)
+    return fused_add_layer_norm(x, res, norm.weight, norm.bias, norm.eps)
+
+
 class Block(nn.Module):
     """Pre-LN transformer block: x + Attn(LN1(x)); x + MLP(LN2(x))
     (timm Block as configured at reference run_vit_training.py:134-141).
@@ -247,12 +273,16 @@ class Block(nn.Module):
         add kernels remain anywhere in the block stack.  The bf16
         rounding of every sum matches the plain add exactly (ln_add
         rounds the fp32 sum to bf16 the same way torch's add does).
+
+    norm_type "rmsnorm" makes norm1 and norm2 ops.RMSNorm (weight only,
+    csrc/rmsnorm.hip), with the same fused residual adds; qk_norm keeps
+    its per-head LayerNorm under either value.
     """
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True,
                  drop=0.0, attn_drop=0.0, deferred_residual=False,
                  drop_path=0.0, qk_norm=False, layer_scale_init=0.0,
-                 mlp_type="gelu"):
+                 mlp_type="gelu", norm_type="layernorm"):
         super().__init__()
         if layer_scale_init < 0:
             raise ValueError(
@@ -265,12 +295,12 @@ class Block(nn.Module):
             )
         self.deferred_residual = deferred_residual
         self.drop_path = drop_path
-        self.norm1 = LayerNorm(dim, eps=1e-6)
+        self.norm1 = make_norm(norm_type, dim)
         self.attn = Attention(
             dim, num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop,
             proj_drop=drop, qk_norm=qk_norm,
         )
-        self.norm2 = LayerNorm(dim, eps=1e-6)
+        self.norm2 = make_norm(norm_type, dim)
         hidden_dim = (swiglu_hidden_dim(dim, mlp_ratio)
                       if mlp_type == "swiglu" else int(dim * mlp_ratio))
         self.mlp = Mlp(dim, hidden_dim, drop=drop, mlp_type=mlp_type)
@@ -307,17 +337,12 @@ class Block(nn.Module):
         if self.deferred_residual and isinstance(x, (tuple, list)):
             hidden, stream = x
             # previous block's MLP residual add, fused into our norm1
-            s0, y0 = fused_add_layer_norm(
-                stream, hidden, self.norm1.weight, self.norm1.bias,
-                self.norm1.eps,
-            )
+            s0, y0 = apply_norm(self.norm1, stream, hidden)
         else:  # plain interface, or first block: nothing pending
             s0, y0 = x, self.norm1(x)
         attn_out = self._attn_branch(y0)
         # fused residual add + norm2 (one kernel for x+attn_out and its LN)
-        return fused_add_layer_norm(
-            s0, attn_out, self.norm2.weight, self.norm2.bias, self.norm2.eps
-        )
+        return apply_norm(self.norm2, s0, attn_out)
 
     def mlp_half(self, x, normed):
         """The MLP branch on attn_half's pair; returns what forward does."""
@@ -367,6 +392,7 @@ class FSDPViTModel(nn.Module):
         qk_norm=False,
         layer_scale_init=0.0,
         mlp_type="gelu",
+        norm_type="layernorm",
     ):
         super().__init__()
         self.fuse_residual = fuse_residual
@@ -397,6 +423,7 @@ class FSDPViTModel(nn.Module):
                 qk_norm=qk_norm,
                 layer_scale_init=layer_scale_init,
                 mlp_type=mlp_type,
+                norm_type=norm_type,
             )
             # init BEFORE wrapping: FSDP shards the weights at wrap time
             init_vit_weights(block)
@@ -408,7 +435,7 @@ class FSDPViTModel(nn.Module):
             xdist.master_print(f"built ViT block {idx}")
         self.blocks = nn.Sequential(*blocks)
 
-        self.norm = LayerNorm(embed_dim, eps=1e-6)
+        self.norm = make_norm(norm_type, embed_dim)
         init_vit_weights(self.norm)
         self.head = nn.Linear(embed_dim, num_classes)
 
@@ -418,12 +445,9 @@ class FSDPViTModel(nn.Module):
         x = self.blocks(x)
         if self.fuse_residual:
             # last block's pending MLP residual add fuses into the
-            # final LayerNorm
+            # final norm
             hidden, stream = x
-            _, normed = fused_add_layer_norm(
-                stream, hidden, self.norm.weight, self.norm.bias,
-                self.norm.eps,
-            )
+            _, normed = apply_norm(self.norm, stream, hidden)
         else:
             normed = self.norm(x)
         # mean pooling over the patch sequence instead of a [CLS] token
@@ -433,13 +457,15 @@ class FSDPViTModel(nn.Module):
 
 def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
                      num_classes, in_chans=3, num_heads=None, qk_norm=False,
-                     layer_scale=False, mlp_type="gelu"):
+                     layer_scale=False, mlp_type="gelu",
+                     norm_type="layernorm"):
     """Exact parameter count for the architecture (used by tests; the
     10B default config gives 10,077,917,160 — SURVEY.md §2D).  qk_norm
     adds q_norm and k_norm, 4 * head_dim per block, and needs num_heads;
     layer_scale adds ls1.gamma and ls2.gamma, 2 * embed_dim per block;
     mlp_type "swiglu" has fc1 [2H, e] and fc2 [e, H] with
-    H = swiglu_hidden_dim(e, mlp_ratio)."""
+    H = swiglu_hidden_dim(e, mlp_ratio); norm_type "rmsnorm" has no bias
+    in norm1, norm2 and the final norm, embed_dim less per site."""
     e = embed_dim
     hid = int(e * mlp_ratio)
     fc1_out = hid
@@ -452,7 +478,7 @@ def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
         + e * e + e
         + e * fc1_out + fc1_out
         + hid * e + e
-        + 4 * e
+        + (2 * e if norm_type == "rmsnorm" else 4 * e)
     )
     if qk_norm:
         per_block += 4 * (e // num_heads)
@@ -460,7 +486,7 @@ def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
         per_block += 2 * e
     patch_embed = (in_chans * patch_size * patch_size) * e + e
     pos_embed = t * e
-    final_norm = 2 * e
+    final_norm = e if norm_type == "rmsnorm" else 2 * e
     head = e * num_classes + num_classes
     return num_blocks * per_block + patch_embed + pos_embed + final_norm + head
 
@@ -538,6 +564,7 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
         qk_norm=getattr(cfg, "qk_norm", False),
         layer_scale_init=getattr(cfg, "layer_scale_init", 0.0),
         mlp_type=mlp_type,
+        norm_type=getattr(cfg, "norm_type", "layernorm"),
     )
     # root wrap without grad-ckpt (reference run_vit_training.py:197-199)
     model = fsdp_wrap(model)

@@ -1,5 +1,6 @@
 from ._extension import ext, has_ext, use_hip
 from .layernorm import LayerNorm, layer_norm, fused_add_layer_norm
+from .rmsnorm import RMSNorm, rms_norm, fused_add_rms_norm
 from .attention import attention, attention_qkv, math_attention
 from .cross_entropy import CrossEntropyLoss, cross_entropy
 from .adamw import FusedAdamW
@@ -32,6 +33,9 @@ __all__ = [
     "LayerNorm",
     "layer_norm",
     "fused_add_layer_norm",
+    "RMSNorm",
+    "rms_norm",
+    "fused_add_rms_norm",
     "attention",
     "attention_qkv",
     "math_attention",
