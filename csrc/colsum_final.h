@@ -1,6 +1,7 @@
 // Final step of a two-stage column sum: [n_chunks, cols] fp32 partials
-// -> bf16 column sums, shared by gelu.hip and transpose.hip.  No atomics:
-// each output is one fixed-order sum, so results repeat bit for bit.
+// -> bf16 column sums, launched by colsum_finish (stream_host.h) for every
+// kernel that sums columns.  No atomics: each output is one fixed-order
+// sum, so results repeat bit for bit.
 #pragma once
 
 #include "common.h"

@@ -36,6 +36,10 @@
 #endif
 
 #include "common.h"
+#include "stream_tiles.h"
+#ifndef VITFSDP_KERNELS_ONLY
+#include "stream_host.h"
+#endif
 
 namespace {
 
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void drop_path_kernel(
   long run_end = (long)(sample + 1u) * rows_per_sample;
   while (r < row_end) {
     const long stop = min(run_end, row_end);
-    if (dropout_hash(seed_path, sample, 0u) >= thresh_path) {
+    if (hash_keep(seed_path, thresh_path, sample, 0u)) {
 #pragma unroll 4
       for (; r < stop; ++r) {
         const long i = r * nvec + vc;
@@ -71,8 +75,8 @@ __global__ __launch_bounds__(kBlock) void drop_path_kernel(
         ushort8_t o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const bool keep = !ELEM || dropout_hash(seed_elem, (unsigned)r,
-                                                  c0 + j) >= thresh_elem;
+          const bool keep =
+              !ELEM || hash_keep(seed_elem, thresh_elem, (unsigned)r, c0 + j);
           const float xf = bf16_to_f32(xv[j]);
           if (ADD) {
             // a dropped lane hands x through: x + 0 without a rounding
@@ -115,27 +119,14 @@ VITFSDP_INSTANTIATE_DROP_PATH(true, true)
 #ifndef VITFSDP_KERNELS_ONLY
 namespace {
 
-void check_operand(const torch::Tensor& t, const char* op, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), op, ": ", name,
-              " must be a contiguous GPU tensor");
-  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, op, ": bf16 only, ", name,
-              " is ", t.scalar_type());
-}
-
-// in double, as ops.attention.dropout_mask_reference does
-unsigned hash_thresh(double p) {
-  const uint64_t t64 = (uint64_t)(p * 4294967296.0);
-  return t64 > 4294967295ull ? 4294967295u : (unsigned)t64;
-}
-
 // x, res as in drop_path_kernel; res undefined for the one-input op
 template <bool ADD>
 torch::Tensor launch(const char* op, const torch::Tensor& x,
                      const torch::Tensor& res, long n_samples, double p_path,
                      long seed_path, double p_elem, long seed_elem) {
-  check_operand(x, op, "x");
+  check_bf16_operand(x, op, "x");
   if (ADD) {
-    check_operand(res, op, "res");
+    check_bf16_operand(res, op, "res");
     TORCH_CHECK(x.sizes() == res.sizes() && x.device() == res.device(), op,
                 ": both operands must have one shape and device");
   }
@@ -162,9 +153,7 @@ torch::Tensor launch(const char* op, const torch::Tensor& x,
   const int nvec = (int)(C / 8);
   // row chunking as in dropout.hip: ~8192 blocks in all
   const long grid_x = (nvec + kBlock - 1) / kBlock;
-  long n_chunks = std::min<long>(std::max<long>(8192 / grid_x, 1), 65535);
-  const long rows_per_chunk = (rows + n_chunks - 1) / n_chunks;
-  n_chunks = (rows + rows_per_chunk - 1) / rows_per_chunk;
+  const auto [n_chunks, rows_per_chunk] = chunk_plan(rows, grid_x, 8192, 1);
   auto stream = at::cuda::getCurrentCUDAStream();
   auto kernel = p_elem > 0.0 ? drop_path_kernel<ADD, true>
                              : drop_path_kernel<ADD, false>;

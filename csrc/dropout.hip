@@ -36,6 +36,10 @@
 
 #include "common.h"
 #include "gelu_math.h"
+#include "stream_tiles.h"
+#ifndef VITFSDP_KERNELS_ONLY
+#include "stream_host.h"
+#endif
 
 namespace {
 
@@ -64,7 +68,7 @@ __global__ __launch_bounds__(kBlock) void hidden_dropout_kernel(
     ushort8_t o;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const bool keep = dropout_hash(seed, (unsigned)r, c0 + j) >= thresh;
+      const bool keep = hash_keep(seed, thresh, (unsigned)r, c0 + j);
       const float af = bf16_to_f32(av[j]);
       if (OP == kDrop) {
         o[j] = keep ? f32_to_bf16(af * rscale) : (unsigned short)0;
@@ -102,20 +106,13 @@ VITFSDP_INSTANTIATE_DROPOUT(kGeluDropBwd)
 #ifndef VITFSDP_KERNELS_ONLY
 namespace {
 
-void check_operand(const torch::Tensor& t, const char* op, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), op, ": ", name,
-              " must be a contiguous GPU tensor");
-  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, op, ": bf16 only, ", name,
-              " is ", t.scalar_type());
-}
-
 // a, b as in hidden_dropout_kernel; b undefined for the one-input ops
 template <int OP>
 torch::Tensor launch(const char* op, const torch::Tensor& a,
                      const torch::Tensor& b, double p, long seed) {
-  check_operand(a, op, OP == kGeluDropBwd ? "dy" : "x");
+  check_bf16_operand(a, op, OP == kGeluDropBwd ? "dy" : "x");
   if (OP == kDropAdd || OP == kGeluDropBwd) {
-    check_operand(b, op, OP == kDropAdd ? "res" : "x");
+    check_bf16_operand(b, op, OP == kDropAdd ? "res" : "x");
     TORCH_CHECK(a.sizes() == b.sizes() && a.device() == b.device(), op,
                 ": both operands must have one shape and device");
   }
@@ -130,24 +127,20 @@ torch::Tensor launch(const char* op, const torch::Tensor& a,
   auto out = torch::empty_like(a);
   if (rows == 0) return out;
 
-  // in double, as ops.attention.dropout_mask_reference does
-  const uint64_t t64 = (uint64_t)(p * 4294967296.0);
-  const unsigned thresh = t64 > 4294967295ull ? 4294967295u : (unsigned)t64;
   const float rscale = (float)(1.0 / (1.0 - p));
 
   const int nvec = (int)(C / 8);
   // row chunking: ~8192 blocks in all, so every CU holds its 8 blocks
   // for several rounds and the tail round is a small share
   const long grid_x = (nvec + kBlock - 1) / kBlock;
-  long n_chunks = std::min<long>(std::max<long>(8192 / grid_x, 1), 65535);
-  const long rows_per_chunk = (rows + n_chunks - 1) / n_chunks;
-  n_chunks = (rows + rows_per_chunk - 1) / rows_per_chunk;
+  const auto [n_chunks, rows_per_chunk] = chunk_plan(rows, grid_x, 8192, 1);
   auto stream = at::cuda::getCurrentCUDAStream();
   hipLaunchKernelGGL(
       hidden_dropout_kernel<OP>, dim3((unsigned)grid_x, (unsigned)n_chunks),
       dim3(kBlock), 0, stream, (const ushort8_t*)a.data_ptr(),
       b.defined() ? (const ushort8_t*)b.data_ptr() : nullptr,
-      (ushort8_t*)out.data_ptr(), nvec, rows, rows_per_chunk, thresh, rscale,
+      (ushort8_t*)out.data_ptr(), nvec, rows, rows_per_chunk,
+      hash_thresh(p), rscale,
       (unsigned)seed);
   HIP_CHECK_LAST();
   return out;

@@ -25,25 +25,18 @@
 #include <torch/extension.h>
 #endif
 
-#include "colsum_final.h"  // partials -> bf16 sums, shared with transpose.hip
+#include "colsum_final.h"
 #include "common.h"
 #include "gelu_math.h"  // gelu_bwd_one, gelu_erf_f32: shared with dropout.hip
+#include "stream_tiles.h"
 #ifndef VITFSDP_KERNELS_ONLY
+#include "stream_host.h"
 #include "transpose.h"  // transpose_plan: gelu_fwd_t moves transpose.hip's tiles
 #endif
 
 namespace {
 
 constexpr int kBlock = 256;
-
-// The mask of the DROP instantiations: element (row, col) is kept iff
-// dropout_hash(seed, row, col) >= thresh, and a kept dy is scaled by
-// rscale (thresh and rscale as launch<> in dropout.hip computes them).
-struct DropArgs {
-  unsigned thresh;
-  float rscale;
-  unsigned seed;
-};
 
 // One element of dx.  DROP: the expression of
 // hidden_dropout_kernel<kGeluDropBwd>, a dropped element SELECTED to +0.
@@ -54,7 +47,7 @@ __device__ __forceinline__ unsigned short dgelu_elem(unsigned short dy,
                                                      unsigned row,
                                                      unsigned col) {
   if constexpr (DROP) {
-    const bool keep = dropout_hash(d.seed, row, col) >= d.thresh;
+    const bool keep = hash_keep(d.seed, d.thresh, row, col);
     return keep ? f32_to_bf16(
                       gelu_bwd_one(bf16_to_f32(dy) * d.rscale, bf16_to_f32(x)))
                 : (unsigned short)0;
@@ -90,9 +83,7 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_kernel(
     }
     dx[i] = out;
   }
-  float4* p = reinterpret_cast<float4*>(part + ((long)blockIdx.y * nvec + vc) * 8);
-  p[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  p[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
+  store_partials8(part + ((long)blockIdx.y * nvec + vc) * 8, acc);
 }
 
 // The same, and dx^T [hid, rows] as a third output for the TN weight
@@ -115,7 +106,6 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_kernel(
 // stored by element.
 constexpr int kTRows = 64;
 constexpr int kTCols = 256;
-constexpr int kTSlots = kTCols / 8;
 
 template <bool DROP>
 __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
@@ -123,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
     unsigned short* __restrict__ dx, unsigned short* __restrict__ dxt,
     float* __restrict__ part, long hid, long n_rows, int rows_per_chunk,
     DropArgs drop) {
-  __shared__ ushort8_t tile[kTRows * kTSlots];
+  __shared__ SwizzledTile<kTCols> tile;
   const unsigned short* tile_s = reinterpret_cast<const unsigned short*>(tile);
   const int t = threadIdx.x;
   const long c0 = (long)blockIdx.x * kTCols;
@@ -152,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
           out[j] =
               dgelu_elem<DROP>(dv[j], xv[j], drop, (unsigned)gr, a_c0 + j);
         *reinterpret_cast<ushort8_t*>(dx + i) = out;
-        tile[r * kTSlots + (a_slot ^ ((r >> 3) & 7))] = out;
+        tile_write<kTCols>(tile, r, a_slot, out);
       }
     }
     __syncthreads();
@@ -164,13 +154,14 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
       const int slot = t >> 3, e = t & 7;
       for (int r = rb; r < re; ++r)
         acc += bf16_to_f32(
-            tile_s[r * kTCols + ((slot ^ ((r >> 3) & 7)) << 3) + e]);
+            tile_s[r * kTCols + (tile_slot(r, slot) << 3) + e]);
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int c = c_hi + 32 * k;
       const long gr = tr0 + c_lo * 8;  // first row of this 8-row group
       if (c0 + c < hid && gr < row_end && gr + 8 > row_begin) {
+        // rows 8 c_lo .. 8 c_lo + 7: tile_slot's XOR is c_lo for all of them
         const unsigned short* src =
             tile_s + (c_lo * 8) * kTCols + (((c >> 3) ^ c_lo) << 3) + (c & 7);
         unsigned short* dst = dxt + (c0 + c) * n_rows + gr;
@@ -201,18 +192,9 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_colsum_t_kernel(
 // rounded once to bf16.
 //
 // Compiled without packed fp32 VALU ops (v_pk_mul/add/fma_f32), which the
-// compiler may pair the eight elements of a vector into.  __syncthreads
-// is a header function, compiled with the default target features, and
-// would be called instead of inlined from here: the barrier is by builtin
-// (as in qk_norm.hip).
+// compiler may pair the eight elements of a vector into; hence
+// lds_barrier (stream_tiles.h).
 constexpr int kFTile = 64;
-constexpr int kFSlots = kFTile / 8;
-
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 #ifdef __HIP_DEVICE_COMPILE__
 __attribute__((target("no-packed-fp32-ops")))
@@ -220,7 +202,7 @@ __attribute__((target("no-packed-fp32-ops")))
 __global__ __launch_bounds__(kBlock) void gelu_fwd_t_kernel(
     const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
     long R, long C, int tiles_per_block) {
-  __shared__ ushort8_t tile[kFTile * kFSlots];
+  __shared__ SwizzledTile<kFTile> tile;
   const unsigned short* tile_s = reinterpret_cast<const unsigned short*>(tile);
   const int t = threadIdx.x;
   // load phase: lane -> input row hi + 32k, 16-byte column slot lo;
@@ -246,7 +228,7 @@ __global__ __launch_bounds__(kBlock) void gelu_fwd_t_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           g[j] = f32_to_bf16(gelu_erf_f32(bf16_to_f32(v[j])));
-        tile[r * kFSlots + (lo ^ ((r >> 3) & 7))] = g;
+        tile_write<kFTile>(tile, r, lo, g);
       }
     }
     lds_barrier();
@@ -256,7 +238,7 @@ __global__ __launch_bounds__(kBlock) void gelu_fwd_t_kernel(
       const long r = r0 + lo * 8;
       if (c0 + c < C && r < R) {
         const unsigned short* src =
-            tile_s + (lo * 8) * kFTile + ((c >> 3) ^ lo) * 8 + (c & 7);
+            tile_s + (lo * 8) * kFTile + tile_slot(lo * 8, c >> 3) * 8 + (c & 7);
         unsigned short* dst = y + (c0 + c) * R + r;
         if (vec_store) {  // then r + 8 <= R
           ushort8_t o;
@@ -301,12 +283,8 @@ std::vector<torch::Tensor> gelu_bwd_colsum_run(const char* op,
                                                torch::Tensor dy,
                                                torch::Tensor x, bool with_t,
                                                double p, long seed) {
-  TORCH_CHECK(dy.is_cuda() && x.is_cuda() && dy.is_contiguous() &&
-                  x.is_contiguous(),
-              op, ": contiguous GPU tensors");
-  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 &&
-                  x.scalar_type() == torch::kBFloat16,
-              op, ": bf16 only");
+  check_bf16_operand(dy, op, "dy");
+  check_bf16_operand(x, op, "x");
   TORCH_CHECK(dy.dim() >= 1 && dy.sizes() == x.sizes() &&
                   dy.device() == x.device(),
               op, ": dy and x must have one shape");
@@ -315,17 +293,8 @@ std::vector<torch::Tensor> gelu_bwd_colsum_run(const char* op,
               ": last dim must be a multiple of 8, got ", hid);
   TORCH_CHECK(hid < (1L << 31), op, ": last dim too large");
   const long n = dy.numel() / hid;
-  DropArgs drop = {0u, 1.f, 0u};
-  if (DROP) {
-    TORCH_CHECK(p > 0.0 && p < 1.0, op, ": p must be in (0, 1), got ", p);
-    // the hash takes the flattened row as 32 bits
-    TORCH_CHECK(n < (1L << 32), op, ": rows must be below 2^32");
-    // in double, exactly as launch<> in dropout.hip
-    const uint64_t t64 = (uint64_t)(p * 4294967296.0);
-    drop.thresh = t64 > 4294967295ull ? 4294967295u : (unsigned)t64;
-    drop.rscale = (float)(1.0 / (1.0 - p));
-    drop.seed = (unsigned)seed;
-  }
+  const DropArgs drop =
+      DROP ? drop_args(op, p, seed, n) : DropArgs{0u, 1.f, 0u};
   auto dx = torch::empty_like(dy);
   auto colsum = torch::empty({hid}, dy.options());
   torch::Tensor dxt;
@@ -339,10 +308,7 @@ std::vector<torch::Tensor> gelu_bwd_colsum_run(const char* op,
   // row chunking: ~2048 blocks in all (256 CUs x 8), at least 16 rows
   // per chunk so the partials stay small against the tensor itself
   const int grid_x = (nvec + kBlock - 1) / kBlock;
-  long n_chunks = std::max(1, 2048 / grid_x);
-  long rows_per_chunk = std::max<long>((n + n_chunks - 1) / n_chunks, 16);
-  n_chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-  TORCH_CHECK(n_chunks <= 65535, op, ": too many rows");
+  const auto [n_chunks, rows_per_chunk] = chunk_plan(n, grid_x, 2048, 16);
   auto part = torch::empty({n_chunks, hid},
                            dy.options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -364,11 +330,7 @@ std::vector<torch::Tensor> gelu_bwd_colsum_run(const char* op,
                        n, (int)rows_per_chunk, drop);
   }
   HIP_CHECK_LAST();
-  hipLaunchKernelGGL(colsum_final_kernel, colsum_final_grid(hid),
-                     dim3(kColsumFinalBlock), 0, stream, part.data_ptr<float>(),
-                     (unsigned short*)colsum.data_ptr(), (int)hid,
-                     (int)n_chunks);
-  HIP_CHECK_LAST();
+  colsum_finish(part, colsum, hid, n_chunks, stream);
   if (with_t) return {dx, colsum, dxt};
   return {dx, colsum};
 }
@@ -404,10 +366,8 @@ std::vector<torch::Tensor> gelu_dropout_bwd_colsum_t(torch::Tensor dy,
 // [cols, rows] contiguous, each element F.gelu's (exact erf) in bits.
 torch::Tensor gelu_fwd_t(torch::Tensor x) {
   const char* op = "gelu_fwd_t";
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2, op, ": 2-D GPU tensor expected");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, op, ": bf16 only");
-  TORCH_CHECK(x.is_contiguous(), op,
-              ": input must be contiguous (no silent copy)");
+  check_bf16_operand(x, op, "input");
+  TORCH_CHECK(x.dim() == 2, op, ": 2-D tensor expected");
   const long R = x.size(0), C = x.size(1);
   TORCH_CHECK(C > 0 && C % 8 == 0, op,
               ": columns must be a multiple of 8, got ", C);

@@ -71,20 +71,13 @@
                              apply_to = function)
 #endif
 
+#include "stream_tiles.h"
+
 namespace {
 
 constexpr int kBlock = 128;
 
 enum ScaleOp { kScale = 0, kScaleAdd = 1, kScaleBwd = 2 };
-
-typedef float float4_t __attribute__((ext_vector_type(4)));
-
-// by builtin: the HIP headers' plain-inline device functions are
-// compiled with the default target features and would be called, not
-// inlined, from the kernels of this file (see qk_norm.hip)
-__device__ __forceinline__ float widen(unsigned short u) {
-  return __builtin_bit_cast(float, (unsigned)u << 16);
-}
 
 // a: the branch x (kScale), the residual stream x (kScaleAdd), dy (kScaleBwd)
 // b: the branch res (kScaleAdd) or branch (kScaleBwd); unused in kScale
@@ -120,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void layer_scale_kernel(
   long r = row_begin;
   while (r < row_end) {
     const long stop = run_end < row_end ? run_end : row_end;
-    if (!PATH || dropout_hash(seed_path, sample, 0u) >= thresh_path) {
+    if (!PATH || hash_keep(seed_path, thresh_path, sample, 0u)) {
 #pragma unroll 4
       for (; r < stop; ++r) {
         const long i = r * nvec + vc;
@@ -130,8 +123,8 @@ __global__ __launch_bounds__(kBlock) void layer_scale_kernel(
         ushort8_t o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const bool keep = !ELEM || dropout_hash(seed_elem, (unsigned)r,
-                                                  c0 + j) >= thresh_elem;
+          const bool keep =
+              !ELEM || hash_keep(seed_elem, thresh_elem, (unsigned)r, c0 + j);
           const float af = widen(av[j]);
           if (OP == kScaleAdd) {
             // a dropped lane hands x through: x + 0 without a rounding
@@ -195,20 +188,9 @@ VITFSDP_INSTANTIATE_LAYER_SCALE_OP(kScaleBwd)
 #endif
 
 #ifndef VITFSDP_KERNELS_ONLY
+#include "stream_host.h"
+
 namespace {
-
-void check_operand(const torch::Tensor& t, const char* op, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), op, ": ", name,
-              " must be a contiguous GPU tensor");
-  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, op, ": bf16 only, ", name,
-              " is ", t.scalar_type());
-}
-
-// in double, as ops.attention.dropout_mask_reference does
-unsigned hash_thresh(double p) {
-  const uint64_t t64 = (uint64_t)(p * 4294967296.0);
-  return t64 > 4294967295ull ? 4294967295u : (unsigned)t64;
-}
 
 // a, b as in layer_scale_kernel (b undefined for kScale), named for the
 // messages; returns {out} or {dbranch, dgamma}
@@ -219,9 +201,9 @@ std::vector<torch::Tensor> launch(const char* op, const torch::Tensor& a,
                                   const torch::Tensor& gamma, long n_samples,
                                   double p_path, long seed_path, double p_elem,
                                   long seed_elem) {
-  check_operand(a, op, a_name);
+  check_bf16_operand(a, op, a_name);
   if (OP != kScale) {
-    check_operand(b, op, b_name);
+    check_bf16_operand(b, op, b_name);
     TORCH_CHECK(a.sizes() == b.sizes() && a.device() == b.device(), op, ": ",
                 a_name, " and ", b_name,
                 " must have one shape and device");
@@ -234,7 +216,7 @@ std::vector<torch::Tensor> launch(const char* op, const torch::Tensor& a,
   const long C = a.size(-1);
   TORCH_CHECK(C > 0 && C % 8 == 0, op, ": last dim of ", a_name,
               " must be a multiple of 8, got ", C);
-  check_operand(gamma, op, "gamma");
+  check_bf16_operand(gamma, op, "gamma");
   TORCH_CHECK(gamma.dim() == 1 && gamma.size(0) == C &&
                   gamma.device() == a.device(),
               op, ": gamma must have shape [", C, "] on the device of ",
@@ -265,10 +247,8 @@ std::vector<torch::Tensor> launch(const char* op, const torch::Tensor& a,
   // of at least 16 rows
   const long target = OP == kScaleBwd ? 2048 : 8192;
   const long min_rows = OP == kScaleBwd ? 16 : 4;
-  long n_chunks = std::min<long>(std::max<long>(target / grid_x, 1), 65535);
-  const long rows_per_chunk =
-      std::max<long>((rows + n_chunks - 1) / n_chunks, min_rows);
-  n_chunks = (rows + rows_per_chunk - 1) / rows_per_chunk;
+  const auto [n_chunks, rows_per_chunk] =
+      chunk_plan(rows, grid_x, target, min_rows);
 
   torch::Tensor part, dgamma;
   if (OP == kScaleBwd) {
@@ -293,12 +273,7 @@ std::vector<torch::Tensor> launch(const char* op, const torch::Tensor& a,
       (unsigned)seed_path, hash_thresh(p_elem), (unsigned)seed_elem, rscale);
   HIP_CHECK_LAST();
   if (OP != kScaleBwd) return {out};
-  hipLaunchKernelGGL(colsum_final_kernel, colsum_final_grid(C),
-                     dim3(kColsumFinalBlock), 0, stream,
-                     part.data_ptr<float>(),
-                     (unsigned short*)dgamma.data_ptr(), (int)C,
-                     (int)n_chunks);
-  HIP_CHECK_LAST();
+  colsum_finish(part, dgamma, C, n_chunks, stream);
   return {out, dgamma};
 }
 

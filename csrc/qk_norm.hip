@@ -60,6 +60,8 @@
                              apply_to = function)
 #endif
 
+#include "stream_tiles.h"  // widen
+
 namespace {
 
 constexpr int kL = 4;                              // lanes per row
@@ -87,9 +89,6 @@ __device__ __forceinline__ float as_f32(unsigned u) {
 }
 __device__ __forceinline__ int as_i32(float f) {
   return __builtin_bit_cast(int, f);
-}
-__device__ __forceinline__ float widen(unsigned short u) {
-  return as_f32((unsigned)u << 16);
 }
 
 // sum over the 4 lanes of a group; every lane gets the same bits (each
@@ -383,6 +382,8 @@ VITFSDP_INSTANTIATE_QK_NORM(6)
 #endif
 
 #ifndef VITFSDP_KERNELS_ONLY
+#include "stream_host.h"
+
 namespace {
 
 // Operand checks, as in layernorm.hip: the kernels read raw pointers with
@@ -533,12 +534,7 @@ std::vector<torch::Tensor> qk_norm_bwd(torch::Tensor dqkv, torch::Tensor qkv,
         wlk.n_iters, wlk.step_tok, wlk.step_h, 1.f / d);
   });
   HIP_CHECK_LAST();
-  hipLaunchKernelGGL(colsum_final_kernel, colsum_final_grid(4 * d),
-                     dim3(kColsumFinalBlock), 0, stream,
-                     part.data_ptr<float>(),
-                     (unsigned short*)grads.data_ptr(), (int)(4 * d),
-                     wlk.n_blocks);
-  HIP_CHECK_LAST();
+  colsum_finish(part, grads, 4 * d, wlk.n_blocks, stream);
   return {grads[0], grads[1], grads[2], grads[3]};
 }
 

@@ -244,6 +244,8 @@ VITFSDP_INSTANTIATE_RMS(4, true)
 }  // namespace
 
 #ifndef VITFSDP_KERNELS_ONLY
+#include "stream_host.h"
+
 namespace {
 
 // Operand checks.  The kernels read raw bf16 / fp32 pointers with sizes
@@ -353,11 +355,7 @@ void launch_bwd(const torch::Tensor& dy, const torch::Tensor* dsum,
         dw_part.data_ptr<float>(), nvec, n, 1.f / d);
   });
   HIP_CHECK_LAST();
-  hipLaunchKernelGGL(colsum_final_kernel, colsum_final_grid(d),
-                     dim3(kColsumFinalBlock), 0, stream,
-                     dw_part.data_ptr<float>(),
-                     (unsigned short*)dw.data_ptr(), d, n_blocks);
-  HIP_CHECK_LAST();
+  colsum_finish(dw_part, dw, d, n_blocks, stream);
 }
 
 }  // namespace

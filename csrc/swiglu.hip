@@ -34,8 +34,8 @@
 // bits.
 //
 // DROP instantiations (hidden dropout behind the activation): element
-// (row, col in [0, H)) is kept iff dropout_hash(seed, row, col) >= thresh,
-// thresh and rscale as in gelu.hip.  The backward takes the plain da: the
+// (row, col in [0, H)) is kept by hash_keep (stream_tiles.h).  The
+// backward takes the plain da: the
 // mask and the scale are applied here, to both halves.
 
 #ifndef VITFSDP_KERNELS_ONLY
@@ -57,30 +57,11 @@
                              apply_to = function)
 #endif
 
+#include "stream_tiles.h"
+
 namespace {
 
 constexpr int kBlock = 256;
-
-typedef float float4_t __attribute__((ext_vector_type(4)));
-
-struct DropArgs {
-  unsigned thresh;
-  float rscale;
-  unsigned seed;
-};
-
-// By builtin: the HIP headers' plain-inline device functions are compiled
-// with the default target features and would be called, not inlined, from
-// the kernels of this file (see qk_norm.hip).
-__device__ __forceinline__ float widen(unsigned short u) {
-  return __builtin_bit_cast(float, (unsigned)u << 16);
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // expf(-g) overflows to +inf from g < -88.7: s is then +0 and every
 // product below a signed zero, the limit.
@@ -109,7 +90,7 @@ __device__ __forceinline__ unsigned short swiglu_elem(unsigned short g,
                                                       unsigned row,
                                                       unsigned col) {
   if constexpr (DROP) {
-    const bool keep = dropout_hash(d.seed, row, col) >= d.thresh;
+    const bool keep = hash_keep(d.seed, d.thresh, row, col);
     return keep ? f32_to_bf16(swiglu_one(widen(g), widen(u)) * d.rscale)
                 : (unsigned short)0;
   } else {
@@ -127,7 +108,7 @@ __device__ __forceinline__ void dswiglu_elem(unsigned short da,
                                              unsigned short& du) {
   float fg, fu;
   if constexpr (DROP) {
-    const bool keep = dropout_hash(d.seed, row, col) >= d.thresh;
+    const bool keep = hash_keep(d.seed, d.thresh, row, col);
     dswiglu_pair(widen(da) * d.rscale, widen(g), widen(u), fg, fu);
     dg = keep ? f32_to_bf16(fg) : (unsigned short)0;
     du = keep ? f32_to_bf16(fu) : (unsigned short)0;
@@ -196,14 +177,9 @@ __global__ __launch_bounds__(kBlock) void swiglu_bwd_colsum_kernel(
     dh[ig] = og;
     dh[iu] = ou;
   }
-  // (make_float4 is a header function: see widen)
   float* pg = part + ((long)blockIdx.y * 2 * nvec + vc) * 8;
-  float4_t* p = reinterpret_cast<float4_t*>(pg);
-  p[0] = float4_t{acc_g[0], acc_g[1], acc_g[2], acc_g[3]};
-  p[1] = float4_t{acc_g[4], acc_g[5], acc_g[6], acc_g[7]};
-  p = reinterpret_cast<float4_t*>(pg + (long)nvec * 8);
-  p[0] = float4_t{acc_u[0], acc_u[1], acc_u[2], acc_u[3]};
-  p[1] = float4_t{acc_u[4], acc_u[5], acc_u[6], acc_u[7]};
+  store_partials8(pg, acc_g);
+  store_partials8(pg + (long)nvec * 8, acc_u);
 }
 
 // The same, and dh^T [2H, rows] as a third output.  A block owns kTHalf
@@ -313,12 +289,11 @@ __global__ __launch_bounds__(kBlock) void swiglu_bwd_colsum_t_kernel(
 // grid and ragged-edge guards over the OUTPUT's [R, H], with two loads per
 // tile vector.
 constexpr int kFTile = 64;
-constexpr int kFSlots = kFTile / 8;
 
 __global__ __launch_bounds__(kBlock) void swiglu_fwd_t_kernel(
     const unsigned short* __restrict__ h, unsigned short* __restrict__ y,
     long R, long H, int tiles_per_block) {
-  __shared__ ushort8_t tile[kFTile * kFSlots];
+  __shared__ SwizzledTile<kFTile> tile;
   const unsigned short* tile_s = reinterpret_cast<const unsigned short*>(tile);
   const DropArgs no_drop = {0u, 1.f, 0u};
   const int t = threadIdx.x;
@@ -346,7 +321,7 @@ __global__ __launch_bounds__(kBlock) void swiglu_fwd_t_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           o[j] = swiglu_elem<false>(gv[j], uv[j], no_drop, 0u, 0u);
-        tile[r * kFSlots + (lo ^ ((r >> 3) & 7))] = o;
+        tile_write<kFTile>(tile, r, lo, o);
       }
     }
     lds_barrier();
@@ -356,7 +331,7 @@ __global__ __launch_bounds__(kBlock) void swiglu_fwd_t_kernel(
       const long r = r0 + lo * 8;
       if (c0 + c < H && r < R) {
         const unsigned short* src =
-            tile_s + (lo * 8) * kFTile + ((c >> 3) ^ lo) * 8 + (c & 7);
+            tile_s + (lo * 8) * kFTile + tile_slot(lo * 8, c >> 3) * 8 + (c & 7);
         unsigned short* dst = y + (c0 + c) * R + r;
         if (vec_store) {  // then r + 8 <= R
           ushort8_t o;
@@ -394,14 +369,14 @@ VITFSDP_INSTANTIATE_SWIGLU(true)
 #endif
 
 #ifndef VITFSDP_KERNELS_ONLY
+#include "stream_host.h"
+
 namespace {
 
 // What every entry point asks of h: bf16 [.., 2H] contiguous on the GPU,
 // 16-byte aligned, H % 8 == 0.  Returns H.
 long check_h(const char* op, const torch::Tensor& h) {
-  TORCH_CHECK(h.is_cuda() && h.is_contiguous(), op,
-              ": contiguous GPU tensors (no silent copy)");
-  TORCH_CHECK(h.scalar_type() == torch::kBFloat16, op, ": bf16 only");
+  check_bf16_operand(h, op, "h");
   TORCH_CHECK(h.dim() >= 1 && h.size(-1) > 0 && h.size(-1) % 2 == 0, op,
               ": h's last dim must be 2H (even), got ",
               h.dim() ? h.size(-1) : 0);
@@ -413,39 +388,14 @@ long check_h(const char* op, const torch::Tensor& h) {
   return H;
 }
 
-DropArgs drop_args(const char* op, bool drop_on, double p, long seed, long n) {
-  DropArgs drop = {0u, 1.f, 0u};
-  if (drop_on) {
-    TORCH_CHECK(p > 0.0 && p < 1.0, op, ": p must be in (0, 1), got ", p);
-    // the hash takes the flattened row as 32 bits
-    TORCH_CHECK(n < (1L << 32), op, ": rows must be below 2^32");
-    // in double, exactly as launch<> in dropout.hip
-    const uint64_t t64 = (uint64_t)(p * 4294967296.0);
-    drop.thresh = t64 > 4294967295ull ? 4294967295u : (unsigned)t64;
-    drop.rscale = (float)(1.0 / (1.0 - p));
-    drop.seed = (unsigned)seed;
-  } else {
-    TORCH_CHECK(p == 0.0, op, ": p must be in [0, 1), got ", p);
-  }
-  return drop;
+// p == 0: no mask
+DropArgs drop_args_or_none(const char* op, double p, long seed, long n) {
+  return p != 0.0 ? drop_args(op, p, seed, n) : DropArgs{0u, 1.f, 0u};
 }
 
 // Row chunks of the walking kernels: ~2048 blocks in all (256 CUs x 8), at
 // least 16 rows per chunk so the partials stay small against the tensor.
-struct ChunkPlan {
-  int grid_x;
-  long n_chunks;
-  long rows_per_chunk;
-};
-
-ChunkPlan chunk_plan(const char* op, long n, long H) {
-  const int grid_x = (int)((H / 8 + kBlock - 1) / kBlock);
-  long n_chunks = std::max(1, 2048 / grid_x);
-  const long rows_per_chunk = std::max<long>((n + n_chunks - 1) / n_chunks, 16);
-  n_chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-  TORCH_CHECK(n_chunks <= 65535, op, ": too many rows");
-  return {grid_x, n_chunks, rows_per_chunk};
-}
+constexpr long kWalkBlocks = 2048, kWalkMinRows = 16;
 
 std::vector<int64_t> with_last(const torch::Tensor& t, long last) {
   auto sizes = t.sizes().vec();
@@ -457,10 +407,8 @@ std::vector<torch::Tensor> swiglu_bwd_run(const char* op, torch::Tensor da,
                                           torch::Tensor h, bool with_t,
                                           double p, long seed) {
   const long H = check_h(op, h);
-  TORCH_CHECK(da.is_cuda() && da.is_contiguous() &&
-                  da.device() == h.device(),
-              op, ": contiguous GPU tensors (no silent copy)");
-  TORCH_CHECK(da.scalar_type() == torch::kBFloat16, op, ": bf16 only");
+  check_bf16_operand(da, op, "da");
+  TORCH_CHECK(da.device() == h.device(), op, ": da must be on h's device");
   TORCH_CHECK(da.dim() == h.dim() && da.sizes().vec() == with_last(h, H), op,
               ": da must be h's shape with H as the last dim");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(da.data_ptr()) % 16 == 0, op,
@@ -468,7 +416,7 @@ std::vector<torch::Tensor> swiglu_bwd_run(const char* op, torch::Tensor da,
   const long n = da.numel() / H;
   const bool drop_on = p != 0.0;
   TORCH_CHECK(!(with_t && drop_on), op, ": dh^T is made with p == 0 only");
-  const DropArgs drop = drop_args(op, drop_on, p, seed, n);
+  const DropArgs drop = drop_args_or_none(op, p, seed, n);
   auto dh = torch::empty_like(h);
   auto colsum = torch::empty({2 * H}, h.options());
   torch::Tensor dht;
@@ -478,7 +426,8 @@ std::vector<torch::Tensor> swiglu_bwd_run(const char* op, torch::Tensor da,
     return with_t ? std::vector<torch::Tensor>{dh, colsum, dht}
                   : std::vector<torch::Tensor>{dh, colsum};
   }
-  const ChunkPlan cp = chunk_plan(op, n, H);
+  const int grid_x = (int)((H / 8 + kBlock - 1) / kBlock);
+  const ChunkPlan cp = chunk_plan(n, grid_x, kWalkBlocks, kWalkMinRows);
   auto part = torch::empty({cp.n_chunks, 2 * H},
                            h.options().dtype(torch::kFloat32));
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -494,25 +443,21 @@ std::vector<torch::Tensor> swiglu_bwd_run(const char* op, torch::Tensor da,
         (int)cp.rows_per_chunk);
   } else if (drop_on) {
     hipLaunchKernelGGL(swiglu_bwd_colsum_kernel<true>,
-                       dim3(cp.grid_x, (unsigned)cp.n_chunks), dim3(kBlock), 0,
+                       dim3(grid_x, (unsigned)cp.n_chunks), dim3(kBlock), 0,
                        stream, (const ushort8_t*)da.data_ptr(),
                        (const ushort8_t*)h.data_ptr(),
                        (ushort8_t*)dh.data_ptr(), part.data_ptr<float>(), nvec,
                        n, (int)cp.rows_per_chunk, drop);
   } else {
     hipLaunchKernelGGL(swiglu_bwd_colsum_kernel<false>,
-                       dim3(cp.grid_x, (unsigned)cp.n_chunks), dim3(kBlock), 0,
+                       dim3(grid_x, (unsigned)cp.n_chunks), dim3(kBlock), 0,
                        stream, (const ushort8_t*)da.data_ptr(),
                        (const ushort8_t*)h.data_ptr(),
                        (ushort8_t*)dh.data_ptr(), part.data_ptr<float>(), nvec,
                        n, (int)cp.rows_per_chunk, drop);
   }
   HIP_CHECK_LAST();
-  hipLaunchKernelGGL(colsum_final_kernel, colsum_final_grid(2 * H),
-                     dim3(kColsumFinalBlock), 0, stream, part.data_ptr<float>(),
-                     (unsigned short*)colsum.data_ptr(), (int)(2 * H),
-                     (int)cp.n_chunks);
-  HIP_CHECK_LAST();
+  colsum_finish(part, colsum, 2 * H, cp.n_chunks, stream);
   if (with_t) return {dh, colsum, dht};
   return {dh, colsum};
 }
@@ -526,11 +471,12 @@ torch::Tensor swiglu_fwd(torch::Tensor h, double p, long seed) {
   const long H = check_h(op, h);
   const long n = h.numel() / (2 * H);
   const bool drop_on = p != 0.0;
-  const DropArgs drop = drop_args(op, drop_on, p, seed, n);
+  const DropArgs drop = drop_args_or_none(op, p, seed, n);
   auto a = torch::empty(with_last(h, H), h.options());
   if (n == 0) return a;
-  const ChunkPlan cp = chunk_plan(op, n, H);
-  const dim3 grid(cp.grid_x, (unsigned)cp.n_chunks);
+  const int grid_x = (int)((H / 8 + kBlock - 1) / kBlock);
+  const ChunkPlan cp = chunk_plan(n, grid_x, kWalkBlocks, kWalkMinRows);
+  const dim3 grid(grid_x, (unsigned)cp.n_chunks);
   auto stream = at::cuda::getCurrentCUDAStream();
   if (drop_on) {
     hipLaunchKernelGGL(swiglu_fwd_kernel<true>, grid, dim3(kBlock), 0, stream,

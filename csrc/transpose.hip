@@ -27,7 +27,9 @@
 
 #include "colsum_final.h"
 #include "common.h"
+#include "stream_tiles.h"
 #ifndef VITFSDP_KERNELS_ONLY
+#include "stream_host.h"
 #include "transpose.h"
 #endif
 
@@ -35,13 +37,12 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kTile = 64;  // rows and columns per tile
-constexpr int kSlots = kTile / 8;
 
 template <bool COLSUM>
 __global__ __launch_bounds__(kBlock) void transpose_kernel(
     const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
     float* __restrict__ part, long R, long C, int tiles_per_block) {
-  __shared__ ushort8_t tile[kTile * kSlots];
+  __shared__ SwizzledTile<kTile> tile;
   const unsigned short* tile_s = reinterpret_cast<const unsigned short*>(tile);
   const int t = threadIdx.x;
   // load phase: lane -> input row hi + 32k, 16-byte column slot lo;
@@ -62,13 +63,13 @@ __global__ __launch_bounds__(kBlock) void transpose_kernel(
       ushort8_t v = {0, 0, 0, 0, 0, 0, 0, 0};  // zeros add nothing to a sum
       if (col_ok && r0 + r < R)
         v = *reinterpret_cast<const ushort8_t*>(x + (r0 + r) * C + c0 + lo * 8);
-      tile[r * kSlots + (lo ^ ((r >> 3) & 7))] = v;
+      tile_write<kTile>(tile, r, lo, v);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int c = hi + 32 * k;
-      const int slot = ((c >> 3) ^ lo) * 8 + (c & 7);
+      const int slot = tile_slot(lo * 8, c >> 3) * 8 + (c & 7);
       ushort8_t o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) o[j] = tile_s[(lo * 8 + j) * kTile + slot];
@@ -146,10 +147,8 @@ namespace {
 // x: bf16 [R, C] contiguous, C % 8 == 0.  Returns {x^T} or {x^T, colsum}.
 std::vector<torch::Tensor> transpose_run(const torch::Tensor& x, bool colsum,
                                          const char* what) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2, what, ": 2-D GPU tensor expected");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, what, ": bf16 only");
-  TORCH_CHECK(x.is_contiguous(), what,
-              ": input must be contiguous (no silent copy)");
+  check_bf16_operand(x, what, "input");
+  TORCH_CHECK(x.dim() == 2, what, ": 2-D tensor expected");
   const long R = x.size(0), C = x.size(1);
   TORCH_CHECK(C > 0 && C % 8 == 0, what,
               ": columns must be a multiple of 8, got ", C);
@@ -169,18 +168,13 @@ std::vector<torch::Tensor> transpose_run(const torch::Tensor& x, bool colsum,
     return {y};
   }
   const TransposePlan p = transpose_plan(R, C, what);
-  const long n_chunks = p.n_chunks;
   auto* xp = (const unsigned short*)x.data_ptr();
   auto* yp = (unsigned short*)y.data_ptr();
-  auto part = torch::empty({n_chunks, C}, x.options().dtype(torch::kFloat32));
+  auto part = torch::empty({p.n_chunks, C}, x.options().dtype(torch::kFloat32));
   hipLaunchKernelGGL(transpose_kernel<true>, p.grid, dim3(kBlock), 0, stream,
                      xp, yp, part.data_ptr<float>(), R, C, p.tpb);
   HIP_CHECK_LAST();
-  hipLaunchKernelGGL(colsum_final_kernel, colsum_final_grid(C),
-                     dim3(kColsumFinalBlock), 0, stream,
-                     part.data_ptr<float>(),
-                     (unsigned short*)sums.data_ptr(), (int)C, (int)n_chunks);
-  HIP_CHECK_LAST();
+  colsum_finish(part, sums, C, p.n_chunks, stream);
   return {y, sums};
 }
 
