@@ -72,6 +72,12 @@ std::vector<torch::Tensor> qk_norm_fwd(torch::Tensor qkv, torch::Tensor wq,
 std::vector<torch::Tensor> qk_norm_bwd(torch::Tensor dqkv, torch::Tensor qkv,
                                        torch::Tensor wq, torch::Tensor wk,
                                        torch::Tensor mean, torch::Tensor rstd);
+std::vector<torch::Tensor> qk_rmsnorm_fwd(torch::Tensor qkv, torch::Tensor wq,
+                                          torch::Tensor wk, double eps);
+std::vector<torch::Tensor> qk_rmsnorm_bwd(torch::Tensor dqkv,
+                                          torch::Tensor qkv, torch::Tensor wq,
+                                          torch::Tensor wk,
+                                          torch::Tensor rstd);
 std::vector<torch::Tensor> gelu_bwd_colsum(torch::Tensor dy, torch::Tensor x);
 std::vector<torch::Tensor> gelu_bwd_colsum_t(torch::Tensor dy,
                                              torch::Tensor x);
@@ -215,6 +221,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "parameter gradients are fixed-order fp32 sums rounded to bf16 [D]",
         py::arg("dqkv"), py::arg("qkv"), py::arg("wq"), py::arg("wk"),
         py::arg("mean"), py::arg("rstd"));
+  m.def("qk_rmsnorm_fwd", &qk_rmsnorm_fwd,
+        "(out, rstd): per-head RMSNorm over D, x * rsqrt(mean(x^2) + eps) * "
+        "w, on slices 0 (q) and 1 (k) of the fused projection [B,T,3,H,D], "
+        "each with its own bf16 [D] weight; slice 2 (v) is copied bit for "
+        "bit, so fmha_fwd_qkv reads out unchanged; rstd is fp32 [B,T,2,H]; "
+        "D % 16 == 0, 16 <= D <= 192",
+        py::arg("qkv"), py::arg("wq"), py::arg("wk"), py::arg("eps"));
+  m.def("qk_rmsnorm_bwd", &qk_rmsnorm_bwd,
+        "(dwq, dwk): backward of qk_rmsnorm_fwd; dqkv (the gradient of out) "
+        "is OVERWRITTEN IN PLACE on slices 0 and 1 with the gradient of "
+        "qkv, slice 2 is neither read nor written; the weight gradients are "
+        "fixed-order fp32 sums rounded to bf16 [D]",
+        py::arg("dqkv"), py::arg("qkv"), py::arg("wq"), py::arg("wk"),
+        py::arg("rstd"));
   m.def("gelu_bwd_colsum", &gelu_bwd_colsum,
         "(dx, colsum): exact-erf GELU backward and the bf16 column sums "
         "of dx over all rows (fc1 bias gradient) in one pass",

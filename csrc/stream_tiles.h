@@ -1,7 +1,7 @@
 // Device building blocks of the memory-bound streaming kernels: the
 // counterpart of mfma_tiles.h for dropout.hip, drop_path.hip,
 // layer_scale.hip, gelu.hip, swiglu.hip and transpose.hip (qk_norm.hip
-// takes widen).
+// takes widen, qk_rmsnorm.hip widen and lds_barrier).
 //
 // All __forceinline__ and written with builtins only.  From a kernel
 // compiled without packed fp32 ops by a target attribute, a plain-inline

@@ -11,7 +11,8 @@ if [ $# -gt 0 ]; then SRCS=("$@"); else
   SRCS=(csrc/fmha.hip csrc/wgemm.hip csrc/fgemm.hip csrc/probes.hip
         csrc/layernorm.hip csrc/gelu.hip csrc/dropout.hip
         csrc/drop_path.hip csrc/transpose.hip csrc/qk_norm.hip
-        csrc/layer_scale.hip csrc/swiglu.hip csrc/rmsnorm.hip)
+        csrc/layer_scale.hip csrc/swiglu.hip csrc/rmsnorm.hip
+        csrc/qk_rmsnorm.hip)
 fi
 OUT=$(mktemp -d)
 trap 'rm -rf "$OUT"' EXIT

@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "csrc/cross_entropy.hip",
         "csrc/fmha.hip",
         "csrc/qk_norm.hip",
+        "csrc/qk_rmsnorm.hip",
         "csrc/gelu.hip",
         "csrc/swiglu.hip",
         "csrc/dropout.hip",

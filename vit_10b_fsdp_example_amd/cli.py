@@ -105,7 +105,20 @@ def build_arg_parser():
         help="LayerNorm over head_dim on q and on k before the dot product "
         "(ViT-22B's remedy for attention-logit growth, timm's qk_norm): "
         "adds attn.q_norm / attn.k_norm to every block, 4 * head_dim "
-        "parameters each, so checkpoints with and without it differ",
+        "parameters each, so checkpoints with and without it differ.  "
+        "--qk_norm_type chooses the norm",
+    )
+    parser.add_argument(
+        "--qk_norm_type", choices=("layernorm", "rmsnorm"),
+        default="layernorm",
+        help="the norm of --qk_norm (an error without it): layernorm has "
+        "weight and bias; rmsnorm is x * rsqrt(mean(x^2) + 1e-6) * weight "
+        "with no mean subtraction and no bias (timm's qk_norm with "
+        "norm_layer=RmsNorm), 2 * head_dim parameters per block, on HIP "
+        "kernels for every head dim the attention serves, and with the "
+        "normalised q and k rebuilt in the backward instead of saved.  "
+        "rmsnorm has no attn.q_norm.bias / attn.k_norm.bias entries, so a "
+        "checkpoint written with one type does not load with the other",
     )
     parser.add_argument(
         "--layer_scale_init", type=_non_negative, default=0.0,
@@ -131,8 +144,8 @@ def build_arg_parser():
         "layernorm has weight and bias; rmsnorm is the norm of the LLM-style "
         "ViTs that pair with the swiglu MLP, "
         "y = x * rsqrt(mean(x^2) + 1e-6) * weight with no mean subtraction "
-        "and no bias.  --qk_norm keeps its per-head LayerNorm under either "
-        "value.  rmsnorm has no norm*.bias entries, so a checkpoint written "
+        "and no bias.  The norm of --qk_norm is chosen by --qk_norm_type, "
+        "not by this flag.  rmsnorm has no norm*.bias entries, so a checkpoint written "
         "with one type does not load with the other",
     )
     parser.add_argument(
@@ -145,4 +158,8 @@ def build_arg_parser():
 
 
 def parse_args(argv=None):
-    return build_arg_parser().parse_args(argv)
+    parser = build_arg_parser()
+    args = parser.parse_args(argv)
+    if args.qk_norm_type != "layernorm" and not args.qk_norm:
+        parser.error("--qk_norm_type rmsnorm needs --qk_norm")
+    return args

@@ -101,11 +101,18 @@ class Attention(nn.Module):
     qk_norm (timm's flag of that name, ViT-22B's remedy for attention-
     logit growth): a LayerNorm over head_dim on q and on k before the dot
     product, its parameters shared by all heads.  q_norm and k_norm exist
-    only when it is on."""
+    only when it is on.  qk_norm_type "rmsnorm" makes them ops.RMSNorm
+    (weight only; timm's qk_norm with norm_layer=RmsNorm), on
+    csrc/qk_rmsnorm.hip."""
 
     def __init__(self, dim, num_heads, qkv_bias=True, attn_drop=0.0,
-                 proj_drop=0.0, qk_norm=False):
+                 proj_drop=0.0, qk_norm=False, qk_norm_type="layernorm"):
         super().__init__()
+        if qk_norm_type not in NORM_TYPES:
+            raise ValueError(
+                f"qk_norm_type has to be one of {NORM_TYPES}, but got "
+                f"{qk_norm_type!r}"
+            )
         assert dim % num_heads == 0
         self.num_heads = num_heads
         self.head_dim = dim // num_heads
@@ -118,8 +125,8 @@ class Attention(nn.Module):
         self.proj_drop = HiddenDropout(proj_drop)
         self.qk_norm = qk_norm
         if qk_norm:
-            self.q_norm = LayerNorm(self.head_dim, eps=1e-6)
-            self.k_norm = LayerNorm(self.head_dim, eps=1e-6)
+            self.q_norm = make_norm(qk_norm_type, self.head_dim)
+            self.k_norm = make_norm(qk_norm_type, self.head_dim)
 
     def forward(self, x, skip_proj_drop=False):
         """skip_proj_drop: return the projection output BEFORE proj_drop;
@@ -131,8 +138,10 @@ class Attention(nn.Module):
         qkv = self.qkv(x).reshape(B, T, 3, self.num_heads, self.head_dim)
         qk_norm = None
         if self.qk_norm:
-            qk_norm = (self.q_norm.weight, self.q_norm.bias,
-                       self.k_norm.weight, self.k_norm.bias, self.q_norm.eps)
+            # an RMSNorm has no bias: (wq, None, wk, None, eps)
+            qk_norm = (self.q_norm.weight, getattr(self.q_norm, "bias", None),
+                       self.k_norm.weight, getattr(self.k_norm, "bias", None),
+                       self.q_norm.eps)
         o = attention_qkv(
             qkv,
             self.num_heads,
@@ -224,7 +233,8 @@ NORM_TYPES = ("layernorm", "rmsnorm")
 
 
 def make_norm(norm_type, dim):
-    """The norm module of blocks.N.norm1 / norm2 and the final norm."""
+    """The norm module of blocks.N.norm1 / norm2, the final norm and
+    attn.q_norm / k_norm."""
     if norm_type not in NORM_TYPES:
         raise ValueError(
             f"norm_type has to be one of {NORM_TYPES}, but got {norm_type!r}"
@@ -275,14 +285,15 @@ class Block(nn.Module):
         rounds the fp32 sum to bf16 the same way torch's add does).
 
     norm_type "rmsnorm" makes norm1 and norm2 ops.RMSNorm (weight only,
-    csrc/rmsnorm.hip), with the same fused residual adds; qk_norm keeps
-    its per-head LayerNorm under either value.
+    csrc/rmsnorm.hip), with the same fused residual adds; the norm of
+    qk_norm is chosen by qk_norm_type alone.
     """
 
     def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True,
                  drop=0.0, attn_drop=0.0, deferred_residual=False,
                  drop_path=0.0, qk_norm=False, layer_scale_init=0.0,
-                 mlp_type="gelu", norm_type="layernorm"):
+                 mlp_type="gelu", norm_type="layernorm",
+                 qk_norm_type="layernorm"):
         super().__init__()
         if layer_scale_init < 0:
             raise ValueError(
@@ -298,7 +309,7 @@ class Block(nn.Module):
         self.norm1 = make_norm(norm_type, dim)
         self.attn = Attention(
             dim, num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop,
-            proj_drop=drop, qk_norm=qk_norm,
+            proj_drop=drop, qk_norm=qk_norm, qk_norm_type=qk_norm_type,
         )
         self.norm2 = make_norm(norm_type, dim)
         hidden_dim = (swiglu_hidden_dim(dim, mlp_ratio)
@@ -393,6 +404,7 @@ class FSDPViTModel(nn.Module):
         layer_scale_init=0.0,
         mlp_type="gelu",
         norm_type="layernorm",
+        qk_norm_type="layernorm",
     ):
         super().__init__()
         self.fuse_residual = fuse_residual
@@ -424,6 +436,7 @@ class FSDPViTModel(nn.Module):
                 layer_scale_init=layer_scale_init,
                 mlp_type=mlp_type,
                 norm_type=norm_type,
+                qk_norm_type=qk_norm_type,
             )
             # init BEFORE wrapping: FSDP shards the weights at wrap time
             init_vit_weights(block)
@@ -458,10 +471,11 @@ class FSDPViTModel(nn.Module):
 def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
                      num_classes, in_chans=3, num_heads=None, qk_norm=False,
                      layer_scale=False, mlp_type="gelu",
-                     norm_type="layernorm"):
+                     norm_type="layernorm", qk_norm_type="layernorm"):
     """Exact parameter count for the architecture (used by tests; the
     10B default config gives 10,077,917,160 — SURVEY.md §2D).  qk_norm
-    adds q_norm and k_norm, 4 * head_dim per block, and needs num_heads;
+    adds q_norm and k_norm, 4 * head_dim per block (2 * head_dim with
+    qk_norm_type "rmsnorm", which has no biases), and needs num_heads;
     layer_scale adds ls1.gamma and ls2.gamma, 2 * embed_dim per block;
     mlp_type "swiglu" has fc1 [2H, e] and fc2 [e, H] with
     H = swiglu_hidden_dim(e, mlp_ratio); norm_type "rmsnorm" has no bias
@@ -481,7 +495,7 @@ def count_vit_params(image_size, patch_size, embed_dim, num_blocks, mlp_ratio,
         + (2 * e if norm_type == "rmsnorm" else 4 * e)
     )
     if qk_norm:
-        per_block += 4 * (e // num_heads)
+        per_block += (2 if qk_norm_type == "rmsnorm" else 4) * (e // num_heads)
     if layer_scale:
         per_block += 2 * e
     patch_embed = (in_chans * patch_size * patch_size) * e + e
@@ -565,6 +579,7 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
         layer_scale_init=getattr(cfg, "layer_scale_init", 0.0),
         mlp_type=mlp_type,
         norm_type=getattr(cfg, "norm_type", "layernorm"),
+        qk_norm_type=getattr(cfg, "qk_norm_type", "layernorm"),
     )
     # root wrap without grad-ckpt (reference run_vit_training.py:197-199)
     model = fsdp_wrap(model)

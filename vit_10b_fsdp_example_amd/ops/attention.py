@@ -19,9 +19,12 @@ math composition (matmul + softmax), which is also the numerics
 reference for the kernel tests.
 """
 
+import os
+
 import torch
 
 from ._extension import ext, use_hip
+from .rmsnorm import _composition as _rms_composition
 
 
 def dropout_mask_reference(seed, bh_q, k, p):
@@ -170,6 +173,56 @@ class _QkNormFlashAttentionQkvFn(torch.autograd.Function):
         return dqkv, dwq, dbq, dwk, dbk, None, None, None, None, None
 
 
+# head dims csrc/qk_rmsnorm.hip is instantiated for: those of fmha.hip
+QK_RMSNORM_HEAD_DIMS = tuple(range(16, 193, 16))
+
+
+def _qk_norm_recompute_on():
+    return os.environ.get("VITFSDP_QK_NORM_RECOMPUTE", "1") != "0"
+
+
+class _QkRmsNormFlashAttentionQkvFn(torch.autograd.Function):
+    """--qk_norm_type rmsnorm: per-head RMSNorm of q and k
+    (csrc/qk_rmsnorm.hip) and the strided flash attention as ONE node, with
+    the in-place backward of _QkNormFlashAttentionQkvFn.
+
+    The normalised copy of the projection is NOT saved: the backward runs
+    qk_rmsnorm_fwd again, the same kernel on the same inputs and so the
+    same bits, into a buffer that lives until fmha_bwd_qkv has read it.
+    One qkv-sized activation less per block for one more memory-bound pass.
+    VITFSDP_QK_NORM_RECOMPUTE=0 saves the copy instead (A/B runs and
+    bisection); outputs and gradients are bit-identical either way."""
+
+    @staticmethod
+    def forward(ctx, qkv, wq, wk, eps, num_heads, scale, p_drop, seed):
+        qkv_n, rstd = ext().qk_rmsnorm_fwd(qkv, wq, wk, eps)
+        o, lse = ext().fmha_fwd_qkv(qkv_n, num_heads, scale, p_drop, seed)
+        ctx.recompute = _qk_norm_recompute_on()
+        saved = (qkv, wq, wk, rstd, o, lse)
+        ctx.save_for_backward(*saved if ctx.recompute else saved + (qkv_n,))
+        ctx.eps = eps
+        ctx.num_heads = num_heads
+        ctx.scale = scale
+        ctx.p_drop = p_drop
+        ctx.seed = seed
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, wq, wk, rstd, o, lse, *kept = ctx.saved_tensors
+        if ctx.recompute:
+            qkv_n = ext().qk_rmsnorm_fwd(qkv, wq, wk, ctx.eps)[0]
+        else:
+            (qkv_n,) = kept
+        dqkv = ext().fmha_bwd_qkv(
+            do.contiguous(), qkv_n, o, lse, ctx.num_heads, ctx.scale,
+            ctx.p_drop, ctx.seed,
+        )
+        del qkv_n  # the transient copy goes before the next allocation
+        dwq, dwk = ext().qk_rmsnorm_bwd(dqkv, qkv, wq, wk, rstd)
+        return dqkv, dwq, dwk, None, None, None, None, None
+
+
 def attention_qkv(qkv, num_heads, scale=None, dropout_p=0.0, training=False,
                   qk_norm=None):
     """Attention on the fused qkv projection.
@@ -185,6 +238,13 @@ def attention_qkv(qkv, num_heads, scale=None, dropout_p=0.0, training=False,
     and D in QK_NORM_HEAD_DIMS runs the qk_norm kernels; everything else
     normalises the q and k views with F.layer_norm and goes on as without
     it.
+
+    With both biases None, (wq, None, wk, None, eps), the norm is the
+    RMSNorm x * rsqrt(mean(x^2) + eps) * w (timm's qk_norm with
+    norm_layer=RmsNorm).  GPU bf16 with bf16 weights and D in
+    QK_RMSNORM_HEAD_DIMS runs the qk_rmsnorm kernels; everything else
+    normalises the q and k views with fp32 statistics and one cast back
+    (the composition of ops/rmsnorm.py).
     """
     B, T, three, H, D = qkv.shape
     assert three == 3 and H == num_heads
@@ -197,7 +257,16 @@ def attention_qkv(qkv, num_heads, scale=None, dropout_p=0.0, training=False,
     )
     if qk_norm is not None:
         wq, bq, wk, bk, eps = qk_norm
-        if (use_kernel and D in QK_NORM_HEAD_DIMS
+        rms = bq is None and bk is None
+        if (rms and use_kernel and D in QK_RMSNORM_HEAD_DIMS
+                and _kernel_dtype(wq.dtype) and _kernel_dtype(wk.dtype)):
+            p = dropout_p if training else 0.0
+            seed = _draw_seed() if p > 0.0 else 0
+            return _QkRmsNormFlashAttentionQkvFn.apply(
+                qkv.contiguous(), wq.contiguous(), wk.contiguous(), eps,
+                num_heads, scale, p, seed,
+            )
+        if (not rms and use_kernel and D in QK_NORM_HEAD_DIMS
                 and all(_kernel_dtype(t.dtype) for t in (wq, bq, wk, bk))):
             p = dropout_p if training else 0.0
             seed = _draw_seed() if p > 0.0 else 0
@@ -207,8 +276,12 @@ def attention_qkv(qkv, num_heads, scale=None, dropout_p=0.0, training=False,
                 seed,
             )
         q, k, v = qkv.unbind(2)
-        q = torch.nn.functional.layer_norm(q, (D,), wq, bq, eps)
-        k = torch.nn.functional.layer_norm(k, (D,), wk, bk, eps)
+        if rms:
+            q = _rms_composition(q, wq, eps)
+            k = _rms_composition(k, wk, eps)
+        else:
+            q = torch.nn.functional.layer_norm(q, (D,), wq, bq, eps)
+            k = torch.nn.functional.layer_norm(k, (D,), wk, bk, eps)
         qkv = torch.stack((q, k, v), dim=2)
     if use_kernel:
         p = dropout_p if training else 0.0
