@@ -119,6 +119,12 @@ std::vector<torch::Tensor> layer_scale_bwd(torch::Tensor dy,
                                            torch::Tensor gamma, long n_samples,
                                            double p_path, long seed_path,
                                            double p_elem, long seed_elem);
+std::vector<torch::Tensor> patch_drop_plan(long seed, long B, long T, long K);
+torch::Tensor patch_drop_embed_fwd(torch::Tensor proj, torch::Tensor pos,
+                                   torch::Tensor idx, double p, long seed);
+std::vector<torch::Tensor> patch_drop_embed_bwd(torch::Tensor dy,
+                                                torch::Tensor inv, long T,
+                                                double p, long seed);
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma32_probe(torch::Tensor a, torch::Tensor b);
 torch::Tensor tr16_probe(long mode);
@@ -339,6 +345,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dy"), py::arg("branch"), py::arg("gamma"),
         py::arg("n_samples"), py::arg("p_path"), py::arg("seed_path"),
         py::arg("p_elem"), py::arg("seed_elem"));
+  m.def("patch_drop_plan", &patch_drop_plan,
+        "(idx, inv): the kept tokens of patch dropout on the current device; "
+        "sample b keeps the K of its T tokens with the smallest "
+        "(dropout_hash(seed, b, t), t) pairs; idx int32 [B, K] lists them "
+        "ascending, inv int32 [B, T] holds a kept token's slot in idx and -1 "
+        "for a dropped one; 1 <= K <= T <= 1024; a pure function of its "
+        "arguments",
+        py::arg("seed"), py::arg("B"), py::arg("T"), py::arg("K"));
+  m.def("patch_drop_embed_fwd", &patch_drop_embed_fwd,
+        "dropout(proj + pos[idx]) in one pass: proj bf16 [B, K, E], pos bf16 "
+        "[T, E], idx int32 [B, K], E % 8 == 0; the sum is torch's bf16 add "
+        "bit for bit, and at 0 < p < 1 the result is dropout_fwd of it; "
+        "p == 0 is no dropout",
+        py::arg("proj"), py::arg("pos"), py::arg("idx"), py::arg("p"),
+        py::arg("seed"));
+  m.def("patch_drop_embed_bwd", &patch_drop_embed_bwd,
+        "(dproj, dpos): backward of patch_drop_embed_fwd from one read of dy "
+        "bf16 [B, K, E] and inv int32 [B, T]: dproj = dropout_fwd(dy), or dy "
+        "itself at p == 0; dpos bf16 [T, E] is the sum of dproj over the "
+        "samples that kept the token, in fp32 and in sample order, rounded "
+        "once, zero at a token nobody kept",
+        py::arg("dy"), py::arg("inv"), py::arg("T"), py::arg("p"),
+        py::arg("seed"));
   m.def("mfma_probe", &mfma_probe, "16x16x32 bf16 MFMA layout probe");
   m.def("mfma32_probe", &mfma32_probe, "32x32x16 bf16 MFMA layout probe");
   m.def("tr16_probe", &tr16_probe, "ds_read_b64_tr_b16 semantics probe");

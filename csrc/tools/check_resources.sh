@@ -12,7 +12,7 @@ if [ $# -gt 0 ]; then SRCS=("$@"); else
         csrc/layernorm.hip csrc/gelu.hip csrc/dropout.hip
         csrc/drop_path.hip csrc/transpose.hip csrc/qk_norm.hip
         csrc/layer_scale.hip csrc/swiglu.hip csrc/rmsnorm.hip
-        csrc/qk_rmsnorm.hip)
+        csrc/qk_rmsnorm.hip csrc/patch_drop.hip)
 fi
 OUT=$(mktemp -d)
 trap 'rm -rf "$OUT"' EXIT

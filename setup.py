@@ -31,6 +31,7 @@ ext = CUDAExtension(
         "csrc/dropout.hip",
         "csrc/drop_path.hip",
         "csrc/layer_scale.hip",
+        "csrc/patch_drop.hip",
         "csrc/transpose.hip",
         "csrc/wgemm.hip",
         "csrc/fgemm.hip",

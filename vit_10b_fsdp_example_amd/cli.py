@@ -149,6 +149,15 @@ def build_arg_parser():
         "with one type does not load with the other",
     )
     parser.add_argument(
+        "--patch_drop_rate", type=_rate_below_one, default=0.0,
+        help="patch dropout (timm's patch_drop_rate, the FLIP / MAE recipe): "
+        "in training each sample keeps a random "
+        "K = max(1, int(T * (1 - rate))) of its T patch tokens, in their "
+        "original order, chosen before the patch projection, so the whole "
+        "step runs on K rows per sample; no parameters are added and eval "
+        "is unchanged; 0 <= rate < 1",
+    )
+    parser.add_argument(
         "--profile", action="store_true", dest="profile",
         help="profile a few early steps with torch.profiler (CPU+GPU "
         "kernel timeline) and write a chrome trace + a top-kernel table "

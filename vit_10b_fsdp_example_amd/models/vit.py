@@ -34,7 +34,8 @@ from ..ops import (  # noqa: F401
     HiddenDropout, LayerNorm, NativeLinear, attention_qkv, cross_entropy,
     RMSNorm, drop_path, drop_path_add, dropout_add, fused_add_layer_norm,
     fused_add_rms_norm, gelu_dropout, hidden_dropout, layer_scale,
-    layer_scale_add, swiglu, swiglu_fc2_recompute, swiglu_hidden_dim,
+    layer_scale_add, patch_drop_embed, patch_drop_plan, swiglu,
+    swiglu_fc2_recompute, swiglu_hidden_dim,
 )
 from ..ops.linear import mlp_fc2_recompute_act, mlp_recompute_act_on
 from ..parallel.checkpoint import in_checkpoint_region, n_open_mlp_blocks
@@ -84,12 +85,16 @@ class PatchEmbed(nn.Module):
         self.num_patches = self.grid_size * self.grid_size
         self.proj = nn.Linear(in_chans * patch_size * patch_size, embed_dim)
 
-    def forward(self, x):
+    def forward(self, x, idx=None):
+        """idx [B, K] (patch dropout): project only patch rows idx[b] of
+        sample b, giving [B, K, E]."""
         B, C, H, W = x.shape
         p, g = self.patch_size, self.grid_size
         # [B, C, g, p, g, p] -> [B, g, g, C, p, p] -> [B, T, C*p*p]
         x = x.reshape(B, C, g, p, g, p).permute(0, 2, 4, 1, 3, 5)
         x = x.reshape(B, g * g, C * p * p)
+        if idx is not None:
+            x = x[torch.arange(B, device=x.device)[:, None], idx.long()]
         return self.proj(x)
 
 
@@ -382,7 +387,15 @@ class FSDPViTModel(nn.Module):
     """ViT with nested FSDP + gradient checkpointing injected per block
     (reference run_vit_training.py:99-162): PatchEmbed + learned
     pos-embed (no CLS token) + N blocks + final LN + mean-pool + linear
-    head (mean pooling per arXiv 2106.04560)."""
+    head (mean pooling per arXiv 2106.04560).
+
+    patch_drop_rate (timm's, default 0 = off): in training each sample
+    keeps a random K = max(1, int(T * (1 - rate))) of its T patch tokens,
+    in their original order, chosen BEFORE the patch projection, so every
+    layer from the projection on sees K rows per sample
+    (ops.patch_drop_plan / ops.patch_drop_embed).  It adds no parameters;
+    in eval, or at 0, forward runs exactly the statements it ran without
+    it."""
 
     def __init__(
         self,
@@ -405,9 +418,16 @@ class FSDPViTModel(nn.Module):
         mlp_type="gelu",
         norm_type="layernorm",
         qk_norm_type="layernorm",
+        patch_drop_rate=0.0,
     ):
         super().__init__()
+        if patch_drop_rate < 0 or patch_drop_rate >= 1:
+            raise ValueError(
+                f"patch_drop_rate has to be in [0, 1), but got "
+                f"{patch_drop_rate}"
+            )
         self.fuse_residual = fuse_residual
+        self.patch_drop_rate = patch_drop_rate
 
         self.patch_embed = PatchEmbed(
             img_size=image_size, patch_size=patch_size, in_chans=3,
@@ -452,9 +472,22 @@ class FSDPViTModel(nn.Module):
         init_vit_weights(self.norm)
         self.head = nn.Linear(embed_dim, num_classes)
 
+    def _embed_kept(self, image):
+        """Patch dropout: pos_drop(proj(kept patches) + their pos_embed
+        rows), [B, K, E]."""
+        T = self.patch_embed.num_patches
+        K = max(1, int(T * (1.0 - self.patch_drop_rate)))
+        idx, inv = patch_drop_plan(image.shape[0], T, K, image.device)
+        return patch_drop_embed(
+            self.patch_embed(image, idx), self.pos_embed, idx, inv,
+            self.pos_drop.p, self.training)
+
     def forward(self, image):
-        x = self.patch_embed(image) + self.pos_embed
-        x = self.pos_drop(x)
+        if self.training and self.patch_drop_rate > 0:
+            x = self._embed_kept(image)
+        else:
+            x = self.patch_embed(image) + self.pos_embed
+            x = self.pos_drop(x)
         x = self.blocks(x)
         if self.fuse_residual:
             # last block's pending MLP residual add fuses into the
@@ -580,6 +613,7 @@ def build_fsdp_vit_model(cfg, device, compute_dtype=torch.float32):
         mlp_type=mlp_type,
         norm_type=getattr(cfg, "norm_type", "layernorm"),
         qk_norm_type=getattr(cfg, "qk_norm_type", "layernorm"),
+        patch_drop_rate=getattr(cfg, "patch_drop_rate", 0.0),
     )
     # root wrap without grad-ckpt (reference run_vit_training.py:197-199)
     model = fsdp_wrap(model)

@@ -21,6 +21,10 @@ from .layer_scale import (
     layer_scale, layer_scale_add, layer_scale_add_reference,
     layer_scale_bwd_reference, layer_scale_reference,
 )
+from .patch_drop import (
+    patch_drop_embed, patch_drop_embed_reference, patch_drop_plan,
+    patch_drop_plan_reference,
+)
 from .swiglu import (
     swiglu, swiglu_bwd_reference, swiglu_fc2_recompute, swiglu_hidden_dim,
     swiglu_reference,
@@ -66,6 +70,10 @@ __all__ = [
     "layer_scale_reference",
     "layer_scale_add_reference",
     "layer_scale_bwd_reference",
+    "patch_drop_plan",
+    "patch_drop_embed",
+    "patch_drop_plan_reference",
+    "patch_drop_embed_reference",
     "swiglu",
     "swiglu_fc2_recompute",
     "swiglu_hidden_dim",

@@ -27,10 +27,9 @@ from ._extension import ext, use_hip
 from .rmsnorm import _composition as _rms_composition
 
 
-def dropout_mask_reference(seed, bh_q, k, p):
-    """Bit-exact python reproduction of csrc/fmha.hip dropout_hash for
-    the GPU tests: returns the keep mask (bool) for global row indices
-    ``bh_q`` [rows] x key columns ``k`` [cols] at probability p."""
+def _dropout_hash(seed, bh_q, k):
+    """csrc/common.h dropout_hash bit for bit: the 32-bit hash values
+    (int64 [rows, cols]) of row indices ``bh_q`` x column indices ``k``."""
     M = 0xFFFFFFFF
     qg = bh_q.to(torch.int64).reshape(-1, 1)
     kg = k.to(torch.int64).reshape(1, -1)
@@ -39,9 +38,15 @@ def dropout_mask_reference(seed, bh_q, k, p):
     x = (x * 0x7FEB352D) & M
     x = x ^ (x >> 15)
     x = (x * 0x846CA68B) & M
-    x = x ^ (x >> 16)
+    return x ^ (x >> 16)
+
+
+def dropout_mask_reference(seed, bh_q, k, p):
+    """Bit-exact python reproduction of csrc/fmha.hip dropout_hash for
+    the GPU tests: returns the keep mask (bool) for global row indices
+    ``bh_q`` [rows] x key columns ``k`` [cols] at probability p."""
     thresh = min(int(p * 4294967296.0), 4294967295)
-    return x >= thresh
+    return _dropout_hash(seed, bh_q, k) >= thresh
 
 
 def _draw_seed():
